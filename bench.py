@@ -17,6 +17,11 @@ per-GPU work stays one C3 frame. N=1 is exactly C3.
 
 Counting: rays = closest-hit + shadow queries (numRays of
 pathtraceintegrator.cpp:74,161); Mrays/s = rays of all ranks / max-over-ranks wall time.
+
+A plain run sets up, warms up, times the steps and prints the line. --full adds the legs that
+take runs of their own: the capture frame (visit counts -> algorithmic bytes of the roofline),
+the one-lane frame (each kernel's own duration), the CPU baseline and the stereo cubemap with
+its gather check. --dump-outputs DIR writes the last timed step's frame as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -61,7 +66,18 @@ def parse():
                         "Default: 6 at N>1 (the BASELINE 1/2/4/8-GPU cubemap, gather checked against a one-GPU "
                         "render), 0 at N=1 so a rocprof summary of the default command averages only the C3 "
                         "launches of the roofline kernel")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure: capture frame (--capture), one-lane frame, "
+                        "CPU baseline (--no-cpu-baseline drops it) and the stereo cubemap (--stereo-frames)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed (rank 0's frame, float32, and its "
+                        "ray counts, float64) as DIR/<name>.npy")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps at least 1, --warmup at least 0")
+    if a.stereo_frames and not a.full:
+        p.error("--stereo-frames: the stereo cubemap is a --full leg")
+    return a
 
 
 def launch_ranks(a):
@@ -100,7 +116,7 @@ def main():
         local = local % max(torch.cuda.device_count(), 1)
     torch.cuda.set_device(local)
     if a.stereo_frames is None:
-        a.stereo_frames = 6 if world > 1 else 0
+        a.stereo_frames = 6 if world > 1 and a.full else 0
     if world > 1:
         if backend == "nccl":
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
@@ -111,7 +127,11 @@ def main():
     import yrt
     from yrt import standin
     from yrt.dist import gather_frame
-    xml = ROOT / "scenes" / "_generated" / f"sponza_standin_r{rank}.xml"
+    # the generated scene goes to a temporary directory (removed at exit), not into the tree: a
+    # checkout may be read-only for the user who runs the benchmark
+    import tempfile
+    scratch = tempfile.TemporaryDirectory(prefix="yrt_bench_")
+    xml = Path(scratch.name) / f"sponza_standin_r{rank}.xml"
     standin.write_xml(xml)
     dev = yrt.Device(local)
     args = ["-i", str(xml)] + standin.C3_ARGS + ["-size", str(a.size), str(a.size), "-spp", str(a.spp)]
@@ -125,9 +145,9 @@ def main():
     if a.capacity:
         dev.set_batch_capacity(a.capacity)
 
-    # ---- untimed capture frame: visit counts of the real query streams (roofline bytes)
+    # ---- untimed capture frame (--full): visit counts of the real query streams (roofline bytes)
     per_kind = {}
-    if a.capture > 0:
+    if a.full and a.capture > 0:
         per_kind = visit_counts(a, dev, R, cam, S, T, F, sinfo)
 
     # ---- warmup + timed frames
@@ -190,13 +210,15 @@ def main():
     rays, closest, shadow = tot.tolist()
     elapsed = tmax.item()
     per_rank = rank_times(acc["msRender"] / a.steps, acc["msGather"] / a.steps, world, red_dev, gather)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a, dev, F, info, fb_t if world > 1 and not gather.startswith("C++") else None, st)
 
-    # one more frame, untimed, on one wavefront lane: no two kernels overlap, so its HIP-event
+    # --full: one more frame, untimed, on one wavefront lane: no two kernels overlap, so its HIP-event
     # durations are each kernel's own (what a rocprof --kernel-trace summary averages); the
     # timed frames' per-kernel durations include the time a kernel shares the GPU with the other
     # lane's kernels. Single-rank runs only (every rank of N > 1 would have to join the gather).
     serial = None
-    if world == 1:
+    if a.full and world == 1:
         dev.set_lanes(1)
         dev.rtRenderFrame(R, cam, S, T, F, 0)
         serial = dev.render_stats()
@@ -284,7 +306,7 @@ def main():
                                                "wavefront lanes' kernels overlap, so these are not additive "
                                                "(their sum exceeds ms_per_step)"}}
         cpu = None
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             cpu = cpu_baseline(ses, a)
         out = {
             "metric": f"Mrays/s (Sponza stand-in {a.size}^2 {a.spp}spp, closest+shadow queries)",
@@ -313,6 +335,7 @@ def main():
         print(json.dumps(out), flush=True)
     ses.close()
     dev.close()
+    scratch.cleanup()
     if world > 1:
         dist.destroy_process_group()
     if stereo and stereo.get("gather_check") not in (None, "bit_exact"):
@@ -321,6 +344,36 @@ def main():
 
 def _r4(x):
     return round(x, 4) if isinstance(x, (int, float)) else None
+
+
+DUMP_BUDGET = 64 << 20  # bytes of --dump-outputs, all files together
+
+
+def dump_outputs(a, dev, F, info, gathered, st):
+    """--dump-outputs: what the last timed step left for its caller, on rank 0. frame.npy is the
+    framebuffer as rtMapFrameBuffer returns it (the gathered frame at N > 1), float32 (H, W, c) in the
+    reference's row order; a frame over the budget is written as (n, c) rows of a fixed, seeded
+    sample of its pixels. ray_counts.npy is that step's [closest, shadow] query counts (rank 0's
+    shard at N > 1), float64. The scene, camera and sampler are seeded, so the same arguments give
+    the same inputs on every run."""
+    W, H = info["width"], info["height"]
+    if gathered is not None:  # torch.distributed fallback gather: the RGB8 rows reduced onto rank 0
+        stride = (3 * W + 3) // 4 * 4
+        img = gathered.cpu().numpy().reshape(H, stride)[:, :3 * W].reshape(H, W, 3)
+    else:
+        fmt = ("RGB8", "RGBA8", "RGB_FLOAT32", "RGBA_FLOAT32")[info["framebufferFormat"]]
+        img = dev.framebuffer_array(F, W, H, fmt)
+    frame = img.astype(np.float32)
+    rays = np.array([st["raysClosest"], st["raysShadow"]], np.float64)
+    budget = DUMP_BUDGET - rays.nbytes - 4096  # 4096: the two .npy headers
+    if frame.nbytes > budget:
+        c = frame.shape[2]
+        pix = np.sort(np.random.default_rng(1234).choice(W * H, budget // (4 * c), replace=False))
+        frame = frame.reshape(W * H, c)[pix]
+    out = Path(a.dump_outputs)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "frame.npy", frame)
+    np.save(out / "ray_counts.npy", rays)
 
 
 def rank_times(render_ms, gather_ms, world, red_dev, gather):

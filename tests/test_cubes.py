@@ -284,9 +284,9 @@ def test_process_rccl_gather_equals_single(gpu_device):
 # ----------------------------------------------------------------------------- bench.py N>1 path
 @pytest.mark.gpu
 def test_bench_two_ranks_cubemap_gather_check(tmp_path):
-    """bench.py at N=2 as the driver launches it (torch.distributed.run, one process per rank),
+    """bench.py --full at N=2 as the driver launches it (torch.distributed.run, one process per rank),
     rehearsed with two gloo ranks on this GPU: the line carries the strong-scaling cubemap
-    (default at N>1) and its gather check against rank 0's one-GPU render is bit-exact. RCCL
+    (default of --full at N>1) and its gather check against rank 0's one-GPU render is bit-exact. RCCL
     refuses two ranks on one GPU, so the rehearsal gathers with torch's reduce (the line says
     which); the C++ RCCL gather itself is test_process_rccl_gather_equals_single on >= 2 GPUs."""
     import json
@@ -300,7 +300,7 @@ def test_bench_two_ranks_cubemap_gather_check(tmp_path):
         port = s.getsockname()[1]
     env = dict(os.environ, YRT_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1",
+           "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--full", "--steps", "1",
            "--warmup", "0", "--size", "256", "--spp", "4", "--capture", "0", "--no-cpu-baseline",
            "--stereo-size", "128", "--stereo-spp", "4"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=str(tmp_path))

@@ -7,7 +7,7 @@ TAG=${1:-envab}
 A=${2:-""}
 B=${3:-""}
 ROUNDS=${4:-2}
-ARGS=${5:-"--no-cpu-baseline --steps 3 --capture 0"}
+ARGS=${5:-"--full --no-cpu-baseline --steps 3 --capture 0"}
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 for i in $(seq 1 $ROUNDS); do

@@ -4,7 +4,7 @@
 # usage: tools/gpu_kstats.sh <tag> ["<bench args>"]
 export TMPDIR=/tmp
 TAG=${1:-ks}
-ARGS=${2:-"--no-cpu-baseline --steps 2 --capture 0"}
+ARGS=${2:-"--full --no-cpu-baseline --steps 2 --capture 0"}
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 for d in $R/yulio-raytracer_amd/lib_variants/*/; do

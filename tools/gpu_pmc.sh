@@ -1,7 +1,8 @@
 #!/bin/bash
 # GPU-box: PMC counter passes of the bench workload (one rocprofv3 run per counter group,
 # kernel trace only, each under its own time limit) + the VALU calibration kernel, then
-# tools/pmc_json.py -> gpurun_out/pmc_<tag>/pmc.json (copy to profiles/pmc_c3.json).
+# tools/pmc_json.py -> $YRT_OUT_DIR/pmc_<tag>/pmc.json (default bench_out/ in the tree; copy to
+# profiles/pmc_c3.json).
 # usage: tools/gpu_pmc.sh <tag> ["<bench args>"]
 set -o pipefail
 export TMPDIR=/tmp
@@ -14,8 +15,8 @@ export YRT_PRIMARY=${YRT_PRIMARY:-0}
 export YRT_LANES=${YRT_LANES:-1}
 TAG=${1:-dev}
 ARGS=${2:-""}
-R=$GRAFT_REPO_ROOT
-OUT=$R/gpurun_out/pmc_$TAG
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${YRT_OUT_DIR:-$R/bench_out}/pmc_$TAG
 mkdir -p $OUT
 i=0
 # VALU lane utilization: thread-cycles of VALU work per VALU instruction cycle, if
@@ -30,7 +31,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" \
            "TCC_HIT_sum TCC_MISS_sum" ${LANE:+"$LANE SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE"}; do
   i=$((i+1))
   cd /tmp && timeout -k 10 -s KILL 240 rocprofv3 --pmc $grp --output-format csv -d $OUT/p$i -o run -- \
-     python3 $R/bench.py --steps 1 --warmup 0 --capture 0 --no-cpu-baseline $ARGS > $OUT/p$i.log 2>&1
+     python3 $R/bench.py --full --steps 1 --warmup 0 --capture 0 --no-cpu-baseline $ARGS > $OUT/p$i.log 2>&1
   rc=$?
   echo "pass $i ($grp) rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 $OUT/p$i.log; exit $rc; fi

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${1:-var}
-ARGS=${2:-"--no-cpu-baseline --steps 2"}
+ARGS=${2:-"--full --no-cpu-baseline --steps 2"}
 for d in yulio-raytracer_amd/lib_variants/*/; do
   v=$(basename $d)
   [ -f $d/libdevice_singleray_mi355x.so ] || continue

@@ -2,7 +2,7 @@
 """PMC passes of one bench workload -> profiles/pmc_c3.json (read by bench.py's roofline).
 
 Input: the directory written by tools/gpu_pmc.sh: pass directories p*/ (rocprofv3 --pmc
-counter_collection.csv of `bench.py --steps 1 --warmup 0 --capture 0 --no-cpu-baseline`), the
+counter_collection.csv of `bench.py --full --steps 1 --warmup 0 --capture 0 --no-cpu-baseline`), the
 bench's own JSON line in p*.log (its config, so bench.py can check that the counters belong to
 the config it runs), and calib/ (tools/valu_calib under the SQ pass).
 
@@ -105,7 +105,7 @@ def main(root, out):
                 v["valu_lane_util"] = v["thread_cycles_per_valu_cycle"] / full
                 if "valu_issue_frac" in v:
                     v["useful_valu_frac"] = v["valu_issue_frac"] * v["valu_lane_util"]
-    res = {"source": "rocprofv3 --pmc, one pass per counter group (tools/gpu_pmc.sh), bench.py --steps 1 "
+    res = {"source": "rocprofv3 --pmc, one pass per counter group (tools/gpu_pmc.sh), bench.py --full --steps 1 "
                      "--warmup 0 --capture 0 --no-cpu-baseline",
            "formulas": {"hbm_bytes_per_dispatch": "2*FETCH_SIZE*1024 + WRITE_SIZE*1024",
                         "valu_issue_frac": f"2*SQ_INSTS_VALU / ({SIMDS} SIMDs * GRBM_GUI_ACTIVE/{XCDS}): 2 issue "
