@@ -2661,7 +2661,7 @@ static int count_visits_impl(const void* nodes_, const void* qnodes_, const void
     if (r.tfar >= r.tnear) {
       const V3 inv = v3(safe_inv(r.dir.x), safe_inv(r.dir.y), safe_inv(r.dir.z));
       const float o[3] = {r.org.x, r.org.y, r.org.z}, iv[3] = {inv.x, inv.y, inv.z};
-      /* the kernel's fused slab test (yrt_traverse.h box4_ordered): fma(plane, inv, -org*inv),
+      /* the kernel's fused slab test (yrt_traverse.h ray_slab_consts): fma(plane, inv, -org*inv),
        * far distances widened by 2^-22 * max|org*inv| on top of the robust factor */
       const float oi[3] = {o[0] * iv[0], o[1] * iv[1], o[2] * iv[2]};
       const float margin = fmaxf(fmaxf(fabsf(oi[0]), fabsf(oi[1])), fabsf(oi[2])) * 2.384185791015625e-07f;

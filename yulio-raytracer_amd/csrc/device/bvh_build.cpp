@@ -568,7 +568,8 @@ void build_bvh(const std::vector<float>& v /* 9 floats per triangle */, const st
   if (C.maxStack > stackDepth - 1)
     throw std::runtime_error("BVH traversal stack bound exceeds YRT_STACK_DEPTH");
   // child references pack (index << 5) | count into an int and the traversal addresses a node
-  // as (index << 7) bytes in 32 bits (kernels/yrt_traverse.h box4_ordered): bound both
+  // by a 32-bit byte offset, (index << 6) for the quantized nodes (kernels/yrt_traverse.h
+  // qnode_load) and (index << 7) for the float ones: bound both
   if (C.out.size() >= (size_t(1) << 25))
     throw std::runtime_error("BVH exceeds 2^25 nodes (32-bit node byte offsets)");
   if (leafIds.size() >= (size_t(1) << 26))

@@ -53,7 +53,7 @@ struct GpuCtx {
   // latency-bound shading).
   struct Lane {
     hipStream_t stream = nullptr;
-    DevBuf qPath[2], qOrg[2], qDir[2], qThr[2], hit, hitGeom, pathL, shFirst, sOrg, sDir, sContrib, sOcc, counters, spill;
+    DevBuf qPath[2], qOrg[2], qDir[2], qThr[2], hit, pathL, shFirst, sOrg, sDir, sContrib, sOcc, counters, spill;
     DevBuf qTime[2], sTime;  // ray times (moving scenes only)
     int64_t pathCap = 0, shadowCap = 0;
     // Batches enqueued whose queue counters are not yet accounted, oldest first: a pinned
@@ -174,7 +174,6 @@ struct GpuCtx {
         L.qThr[k].alloc(Q * 16);
       }
       L.hit.alloc(Q * 16);
-      if (trace_hit_geom()) L.hitGeom.alloc(Q * 4);
       L.pathL.alloc(Q * 16);
       L.pathCap = Q;
     }
@@ -784,7 +783,6 @@ void Device::render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vec
         pb.qThr[k] = L.qThr[k].as<float4>();
       }
       pb.hit = L.hit.as<float4>();
-      pb.hitGeom = L.hitGeom.as<int>();
       pb.pathL = L.pathL.as<float4>();
       pb.shFirst = L.shFirst.as<int>();
       pb.sOrg = L.sOrg.as<float4>();
@@ -862,7 +860,7 @@ void Device::render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vec
     const int primMode = getenv("YRT_PRIMARY") ? atoi(getenv("YRT_PRIMARY")) : 1;
     const double primMiss = getenv("YRT_PRIMARY_MISS") ? atof(getenv("YRT_PRIMARY_MISS")) : 0.5;
     // Toe-in stereo cameras (the DLL's FPR default) are left to k_raygen: the fused kernel is
-    // compiled without that branch (camera_ray<false>, pathtrace.hip).
+    // compiled without that branch (camera_ray<false>, kernels/yrt_camera.h).
     bool toeIn = false;
     for (const GpuCamera& c : g.hCams) toeIn |= c.type == CAM_STEREO && c.toeIn != 0;
     const bool fusedPrimary = captureMax == 0 && !G.hasMotion && !fv.backplateTexels && sv.numEnvDir == 0 &&
@@ -913,10 +911,10 @@ void Device::render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vec
           pr.segCap = pb.segCap;
           pr.traced = pb.counters + tracedWord;
           pr.numPaths = (long long)bi.numPixels * spp;
-          launch_trace_primary(lsv, pr, pb.hit, pb.hitGeom, st);
+          launch_trace_primary(lsv, pr, pb.hit, st);
         } else {
           launch_trace_closest(lsv, pb.qOrg[cur], pb.qDir[cur], pb.counters + qcounter_index(d, 0, 0), YRT_QSEGS,
-                               pb.segCap, pb.hit, st, pb.qTime[cur], pb.hitGeom);
+                               pb.segCap, pb.hit, st, pb.qTime[cur]);
         }
         if (kernelTiming) { HIP_CHECK(hipEventRecord(e1.b, st)); evs.push_back(e1); }
         if (captureMax > 0 && J.first == 0)
@@ -1888,8 +1886,7 @@ int yrtGetSceneInfo(YRTDevice dev, YRTHandle scene, YRTSceneInfo* out) {
   out->numNodes = (int64_t)S->gpu->hNodes.size();
   out->numTriRefs = (int64_t)S->gpu->hTris.size();
   out->triRecordBytes = (int64_t)sizeof(GpuTri);
-  out->nodeBytesClosest = trace_node_bytes(false);
-  out->nodeBytesAny = trace_node_bytes(true);
+  out->nodeBytesClosest = out->nodeBytesAny = (int)sizeof(GpuQNode);  // k_trace reads the quantized nodes only
   out->bvhDepth = S->gpu->bvhDepth;
   out->numLights = S->gpu->view.numLights;
   out->buildSeconds = S->gpu->buildSeconds;

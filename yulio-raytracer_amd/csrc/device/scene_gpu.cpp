@@ -270,8 +270,8 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
 
   BvhResult bvh;
   build_bvh(triVerts, triFlags, stackDepth, bvh, anyMotion ? &triVerts1 : nullptr);
-  // each leaf record carries its triangle's geometry id (GpuTri::e2[3]) for the closest-hit
-  // kernels' hitGeom output
+  // each leaf record carries its triangle's geometry id (GpuTri::e2[3]): part of the record's
+  // layout as exported; the kernels take the id from the shading record (GpuTriShade)
   for (size_t i = 0; i < bvh.tris.size(); ++i) memcpy(&bvh.tris[i].e2[3], &triGeom[bvh.order[i]], 4);
   // the any-hit kernels' 64-B nodes (common/yrt_qnode.h), node for node
   std::vector<GpuQNode> qnodes(bvh.nodes.size());

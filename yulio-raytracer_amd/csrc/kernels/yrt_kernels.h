@@ -13,7 +13,7 @@ namespace yrt {
 
 struct SceneView {
   const GpuNode* nodes;
-  const GpuQNode* qnodes;  // the same tree, 64-B quantized nodes (any-hit traversal)
+  const GpuQNode* qnodes;  // the same tree, 64-B quantized nodes (k_trace)
   const GpuTri* tris;
   const int* triGeom;
   const int4* indices;
@@ -50,12 +50,10 @@ struct SceneView {
 #ifndef YRT_TRACE_GRID
 #define YRT_TRACE_GRID 16384
 #endif
-// spilled stack entries per lane: the one-ray kernels' (YRT_STACK_DEPTH - ring), or two ray slots'
-// of k_occluded2 (one 64-lane wave per block, YRT_TRACE_GRID blocks at most)
+// spilled stack entries per lane (YRT_STACK_DEPTH - the smallest LDS ring), for YRT_TRACE_GRID
+// blocks at most
 #define YRT_SPILL_1 (YRT_STACK_DEPTH - YRT_LDS_STACK_MIN)
-#define YRT_SPILL_2 (YRT_ANY2 ? 2 * (YRT_STACK_DEPTH - YRT_ANY2_LDS) : 0)
-#define YRT_TRACE_SPILL_INTS \
-  ((size_t)YRT_TRACE_GRID * (YRT_TRACE_BLOCK > 64 ? YRT_TRACE_BLOCK : 64) * (YRT_SPILL_1 > YRT_SPILL_2 ? YRT_SPILL_1 : YRT_SPILL_2))
+#define YRT_TRACE_SPILL_INTS ((size_t)YRT_TRACE_GRID * (YRT_TRACE_BLOCK > 64 ? YRT_TRACE_BLOCK : 64) * YRT_SPILL_1)
 
 struct FrameView {
   const GpuRenderParams* rp;   // device copy
@@ -101,8 +99,8 @@ struct PathBuffers {
   float4* qDir[2];   // xyz, tfar
   float4* qThr[2];   // throughput xyz, w = meta bits: depth | ignoreVL<<8 | unbent<<9
   float4* hit;       // t, u, v, tri (bits), per closest-queue slot
-  int* hitGeom;      // the hit triangle's geometry id, per closest-queue slot: k_shade loads its
-                     // geometry record beside the shading record instead of after it
+  void* reserved = nullptr;  // unused: keeps the kernel-argument offsets of everything below, which
+                             // k_shade's scalar-load grouping and SGPR spills depend on
   float4* pathL;     // per path id: radiance so far (emission and unoccluded direct light are
                      // read-modify-written in the reference's order; one writer per path at a time)
   int* shFirst;      // per (queue slot, light): shadow-ray slot or -1
@@ -164,14 +162,12 @@ void launch_raygen(const FrameView& fv, const PathBuffers& pb, const BatchInfo& 
 // Every launch gets the full grid for the queue's capacity: the kernels grid-stride over the
 // device-side count and idle waves exit at once.
 // time (moving scenes): per-slot ray time (Ray::time); null: static scene (or time 0)
-// hitGeom (optional): the hit triangle's geometry id per slot
 void launch_trace_closest(const SceneView& sv, const float4* org, const float4* dir, const unsigned* counts,
-                          int numSegs, int segCap, float4* hit, hipStream_t s, const float* time = nullptr,
-                          int* hitGeom = nullptr);
+                          int numSegs, int segCap, float4* hit, hipStream_t s, const float* time = nullptr);
 // depth 0 of a batch: camera rays generated, traced and queued (hits) or resolved (misses) in
 // one kernel, see PrimaryRays; replaces launch_raygen + the depth-0 launch_trace_closest for
 // static scenes without a backplate or direction-dependent environment lights
-void launch_trace_primary(const SceneView& sv, const PrimaryRays& pr, float4* hit, int* hitGeom, hipStream_t s);
+void launch_trace_primary(const SceneView& sv, const PrimaryRays& pr, float4* hit, hipStream_t s);
 void launch_trace_any(const SceneView& sv, const float4* org, const float4* dir, const unsigned* counts, int numSegs,
                       int segCap, int* occluded, hipStream_t s, const ShadowFuse* fuse = nullptr,
                       const float* time = nullptr);
@@ -182,12 +178,12 @@ void launch_shade(const SceneView& sv, const FrameView& fv, const PathBuffers& p
 void launch_shadow_resolve(const PathBuffers& pb, int depth, int numLights, hipStream_t s);
 void launch_resolve_pixels(const FrameView& fv, const PathBuffers& pb, const BatchInfo& bi, float* fbFloat,
                            uint8_t* fbRGB8, int rgb8Stride, float4* accu, int accumulate, hipStream_t s);
-// YRT_PROFILE builds only: SIMD-utilization counters of k_trace (see pathtrace.hip); -1 otherwise
+// YRT_PROFILE builds only: SIMD-utilization counters of k_trace (see yrt_wave.h); -1 otherwise
 int trace_profile(unsigned long long* out8, int reset);
 // Debug capture: per-sample radiance of pixel id (y * width + x) of frame `frame` written to
 // out[s] by the next resolves (pixelId -1: off)
 int debug_pixel_capture(int pixelId, int frame, float4* out, int capacity);
-// Arithmetic self-check of the correctly rounded fast reciprocal (rcp_rn): see pathtrace.hip
+// Arithmetic self-check of the correctly rounded fast reciprocal (rcp_rn): see k_aux.h
 int check_math(int fn, unsigned long long* host2);
 int check_math_table(int fn, const uint16_t* table2048, unsigned long long* host2);
 // Multi-GPU gather (device.cpp): the pixels of the tiles of one shard (job tile =
@@ -216,10 +212,6 @@ void launch_refit_nodes(GpuNode* nodes, const GpuTri* tris, const int4* indices,
                         const int* levelNodes, int count, hipStream_t s);
 // the quantized copy of every node (yrt_quantize_node), after a refit of the float nodes
 void launch_quantize_nodes(const GpuNode* nodes, GpuQNode* qnodes, int count, hipStream_t s);
-// bytes per node of the closest-hit / any-hit traversal as built (YRT_QNODES_CLOSEST / _ANY)
-int trace_node_bytes(bool anyHit);
-// whether the closest-hit kernels store each hit's geometry id (YRT_HIT_GEOM)
-bool trace_hit_geom();
 void launch_debug_render(const SceneView& sv, const FrameView& fv, int maxDepth, int spp, int numTiles, float* fbFloat,
                          uint8_t* fbRGB8, int rgb8Stride, hipStream_t s);
 

@@ -16,7 +16,7 @@
 // banks. Only the top entries live in LDS, a ring of 16 per lane (4 KB per 64-lane block) for
 // every traversal kind since round 6; deeper entries spill to global memory. History: closest
 // hit on the float nodes, 32 entries instead of 16: +4.9 % on C3 in round 1, still +2 % in
-// round 6; on the 64-B quantized nodes 16 entries win (6 waves/SIMD, C3 +5.3 %, pathtrace.hip).
+// round 6; on the 64-B quantized nodes 16 entries win (6 waves/SIMD, C3 +5.3 %, k_trace.h).
 // The builder bounds the tree depth to YRT_STACK_DEPTH-1 (device/bvh_build.cpp).
 #pragma once
 
@@ -49,13 +49,6 @@ static_assert((YRT_LDS_STACK_ANY & (YRT_LDS_STACK_ANY - 1)) == 0, "YRT_LDS_STACK
 static_assert((YRT_LDS_STACK_PRIM & (YRT_LDS_STACK_PRIM - 1)) == 0, "YRT_LDS_STACK_PRIM must be a power of two");
 #define YRT_LDS_STACK_MIN2 (YRT_LDS_STACK < YRT_LDS_STACK_ANY ? YRT_LDS_STACK : YRT_LDS_STACK_ANY)
 #define YRT_LDS_STACK_MIN (YRT_LDS_STACK_MIN2 < YRT_LDS_STACK_PRIM ? YRT_LDS_STACK_MIN2 : YRT_LDS_STACK_PRIM)
-#ifndef YRT_ANY2
-#define YRT_ANY2 0  // 1: static scenes' shadow queries run two rays per lane (k_occluded2)
-#endif
-#ifndef YRT_ANY2_LDS
-#define YRT_ANY2_LDS 16  // LDS ring entries per ray slot of k_occluded2
-#endif
-static_assert((YRT_ANY2_LDS & (YRT_ANY2_LDS - 1)) == 0, "YRT_ANY2_LDS must be a power of two");
 #ifndef YRT_TRACE_BLOCK
 // one wave per block (8 KB of LDS stack): +1.0 % on C3 over 128-lane blocks once the trace code
 // was scheduled for a 6-wave target (profiles/r01/variants_r01.txt)
@@ -87,11 +80,11 @@ __device__ __forceinline__ float safe_inv(float d) {
 struct RayPre {
   V3 org, dir, inv;
   float tnear, tfar;
-  V3 oi;         // org * inv (rounded): slab distances as fma(plane, inv, -oi) (box4_ordered)
-  float margin;  // absolute slack of those distances: 2^-22 * max |oi| (see box4_ordered)
+  V3 oi;         // org * inv (rounded): slab distances as fma(plane, inv, -oi) (box4_qdata)
+  float margin;  // absolute slack of those distances: 2^-22 * max |oi| (see box4_qdata)
 };
 
-// Per-ray constants of box4_ordered's fused slab test.
+// Per-ray constants of box4_qdata's fused slab test.
 __device__ __forceinline__ void ray_slab_consts(const V3& org, const V3& inv, V3& oi, float& margin) {
   oi = v3(org.x * inv.x, org.y * inv.y, org.z * inv.z);
   margin = fmaxf(fmaxf(fabsf(oi.x), fabsf(oi.y)), fabsf(oi.z)) * 2.384185791015625e-07f;  // 2^-22
@@ -129,101 +122,36 @@ __device__ __forceinline__ void box4(const GpuNode* __restrict__ np, const RayPr
 #undef YRT_CHILD
 }
 
-// Same entry distances as box4, with the near/far plane of each axis picked per ray by the
-// sign of its inverse direction instead of a min/max per slab: planeOff packs the byte
-// offsets (0 or 16) of the near plane within the lo/hi pair of x, y, z in bits 0-7, 8-15,
-// 16-23. Rounding is monotonic, so for lo <= hi the ordered planes give bit-identical slab
-// distances to min/max and the traversal is unchanged; it saves 24 VALU ops per node.
+// The wavefront kernel's box test picks the near/far plane of each axis per ray by the sign of
+// its inverse direction instead of a min/max per slab: planeOff holds one bit per axis (16,
+// 16 << 8, 16 << 16 for x, y, z), set when the ray travels toward smaller coordinates, so that
+// the hi plane is the near one. Rounding is monotonic, so for lo <= hi the ordered planes give
+// bit-identical slab distances to min/max; it saves 24 VALU ops per node.
 __device__ __forceinline__ int plane_offsets(float ix, float iy, float iz) {
   return ((__float_as_uint(ix) >> 27) & 16) | ((__float_as_uint(iy) >> 19) & (16 << 8)) |
          ((__float_as_uint(iz) >> 11) & (16 << 16));
 }
-// Empty slots carry inverted infinite boxes (device/bvh_build.cpp), which the ordered-plane
-// test culls by itself, so no child-reference check is needed. The six plane loads and the
-// child load address the node array as a uniform (SGPR) base plus a 32-bit per-lane byte
-// offset (global_load saddr form) instead of six 64-bit per-lane pointers (78/74 VGPRs instead
-// of 82/84). nodeIdx < 2^25 (node byte offsets fit 32 bits; bvh_build.cpp enforces it).
+
+// The wavefront kernel's box test, on the 64-B quantized node (common/yrt_qnode.h) of the float
+// node's index: one 64-B line (four loads: origin + quantum exponents, children, lo/hi words of
+// x and y, of z) instead of seven 16-B loads from 128 B. The loads address the node array as a
+// uniform (SGPR) base plus a 32-bit per-lane byte offset (global_load saddr form), not a 64-bit
+// per-lane pointer; nodeIdx < 2^25 (bvh_build.cpp enforces it).
+// Slab distance t = fma(plane, inv, -org * inv): one fused op per plane instead of a subtract
+// and a multiply. Against (plane - org) * inv it carries an extra absolute error of at most one
+// rounding of org * inv (u * |oi|, u = 2^-24) on each of the near and far distances; the far
+// plane is widened by margin = 4u * max|oi| on top of the robust factor, so the test stays
+// conservative: a box the ray meets is never culled, and the closest hit (smallest (t, triangle
+// id)) is the same for any visit order.
+// Per axis a = fma(origin, inv, -org * inv) and s = 2^e * inv (exact); per plane one
+// v_cvt_f32_ubyte and one FMA (packed two children at a time), the near and far words picked by
+// the ray's direction signs (planeOff). The planes lie at least one quantum outside the float
+// node's child boxes, which covers a's rounding (see yrt_qnode.h), so no box that the float
+// nodes keep is culled and every query returns the same bits. Empty slots are tested by their
+// child reference.
 // MISS: the entry distance reported for a missed child (+INF for closest-hit rays, which sort
 // ascending; -INF for any-hit rays, which visit the farthest child first, see sort3_far).
-// The ray's near/far planes and the child references of one node, as loaded.
-struct NodeData {
-  float4 nx, fx, ny, fy, nz, fz;
-  int4 ch;
-};
-__device__ __forceinline__ NodeData node_load(const GpuNode* __restrict__ base, int nodeIdx, int planeOff) {
-  const char* b0 = (const char*)base;
-  const unsigned nb = (unsigned)nodeIdx << 7;
-  const unsigned ox = (unsigned)planeOff & 0xffu, oy = ((unsigned)planeOff >> 8) & 0xffu,
-                 oz = (unsigned)planeOff >> 16;
-  NodeData d;
-  d.nx = *(const float4*)(b0 + (nb + ox));
-  d.fx = *(const float4*)(b0 + (nb + (16u - ox)));
-  d.ny = *(const float4*)(b0 + (nb + (32u + oy)));
-  d.fy = *(const float4*)(b0 + (nb + (48u - oy)));
-  d.nz = *(const float4*)(b0 + (nb + (64u + oz)));
-  d.fz = *(const float4*)(b0 + (nb + (80u - oz)));
-  d.ch = *(const int4*)(b0 + (nb + 96u));
-  return d;
-}
-template <bool ANY = false>
-__device__ __forceinline__ void box4_data(const NodeData& d, const RayPre& r, float tmax, float t[4], int c[4]);
-template <bool ANY = false>
-__device__ __forceinline__ void box4_ordered(const RayPre& r, int planeOff, float tmax, float t[4], int c[4],
-                                             const GpuNode* __restrict__ base, int nodeIdx) {
-  box4_data<ANY>(node_load(base, nodeIdx, planeOff), r, tmax, t, c);
-}
-template <bool ANY>
-__device__ __forceinline__ void box4_data(const NodeData& d, const RayPre& r, float tmax, float t[4], int c[4]) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  const float4 nx = d.nx, fx = d.fx, ny = d.ny, fy = d.fy, nz = d.nz, fz = d.fz;
-  const int4 ch = d.ch;
-  // slab distance t = fma(plane, inv, -org*inv): one fused op per plane instead of a subtract
-  // and a multiply. Against (plane - org) * inv it carries an extra absolute error of at most
-  // one rounding of org*inv (u * |oi|, u = 2^-24) on each of the near and far distances; the
-  // far plane is widened by margin = 4u * max|oi| on top of the robust factor (relative
-  // errors, as before), so the test stays conservative: a box the ray meets is never culled,
-  // and the closest hit (smallest (t, triangle id)) is the same for any visit order.
-  const f2 ix = {r.inv.x, r.inv.x}, iy = {r.inv.y, r.inv.y}, iz = {r.inv.z, r.inv.z};
-  const f2 mx = {-r.oi.x, -r.oi.x}, my = {-r.oi.y, -r.oi.y}, mz = {-r.oi.z, -r.oi.z};
-#define YRT_SLAB(P, I, M) __builtin_elementwise_fma(P, I, M)
-  const f2 nx01 = YRT_SLAB((f2{nx.x, nx.y}), ix, mx), nx23 = YRT_SLAB((f2{nx.z, nx.w}), ix, mx);
-  const f2 fx01 = YRT_SLAB((f2{fx.x, fx.y}), ix, mx), fx23 = YRT_SLAB((f2{fx.z, fx.w}), ix, mx);
-  const f2 ny01 = YRT_SLAB((f2{ny.x, ny.y}), iy, my), ny23 = YRT_SLAB((f2{ny.z, ny.w}), iy, my);
-  const f2 fy01 = YRT_SLAB((f2{fy.x, fy.y}), iy, my), fy23 = YRT_SLAB((f2{fy.z, fy.w}), iy, my);
-  const f2 nz01 = YRT_SLAB((f2{nz.x, nz.y}), iz, mz), nz23 = YRT_SLAB((f2{nz.z, nz.w}), iz, mz);
-  const f2 fz01 = YRT_SLAB((f2{fz.x, fz.y}), iz, mz), fz23 = YRT_SLAB((f2{fz.z, fz.w}), iz, mz);
-#undef YRT_SLAB
-  const float MISS = __int_as_float(ANY ? 0xff800000 : 0x7f800000);
-  // v_max/v_min written out (+1.5 % on C3, shadow trace 5.84 -> 5.38 ms/launch,
-  // profiles/r02/trace_variants_r02.txt): fmaxf/fminf on the loop-carried tnear / tfar make
-  // the compiler re-quiet (canonicalize) them with an extra v_max every node step (IEEE mode). A signalling
-  // NaN never reaches here (ray records are computed values), and the hardware min/max give
-  // the same result as fmaxf/fminf for every other input.
-#define YRT_CHILD(k, NX, FX, NY, FY, NZ, FZ, CH)                                            \
-  do {                                                                                      \
-    float nn, ff, a_, b_;                                                                   \
-    asm("v_max_f32 %0, %1, %2" : "=v"(a_) : "v"(NZ), "v"(r.tnear));                         \
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(nn) : "v"(NX), "v"(NY), "v"(a_));                \
-    asm("v_min_f32 %0, %1, %2" : "=v"(b_) : "v"(FZ), "v"(tmax));                            \
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(ff) : "v"(FX), "v"(FY), "v"(b_));                \
-    t[k] = nn <= __builtin_fmaf(ff, YRT_BOX_ROBUST, r.margin) ? nn : MISS;                  \
-    c[k] = (CH);                                                                            \
-  } while (0)
-  YRT_CHILD(0, nx01.x, fx01.x, ny01.x, fy01.x, nz01.x, fz01.x, ch.x);
-  YRT_CHILD(1, nx01.y, fx01.y, ny01.y, fy01.y, nz01.y, fz01.y, ch.y);
-  YRT_CHILD(2, nx23.x, fx23.x, ny23.x, fy23.x, nz23.x, fz23.x, ch.z);
-  YRT_CHILD(3, nx23.y, fx23.y, ny23.y, fy23.y, nz23.y, fz23.y, ch.w);
-#undef YRT_CHILD
-}
-
-// box4_ordered on the 64-B quantized node of the same index (common/yrt_qnode.h): one 64-B line
-// (four loads: origin + quantum exponents, children, lo/hi words of x and y, of z) instead of
-// seven 16-B loads from 128 B. Per axis a = fma(origin, inv, -org * inv) and s = 2^e * inv
-// (exact); per plane one v_cvt_f32_ubyte and one FMA (packed two children at a time), the near
-// and far words picked by the ray's direction signs (planeOff, as box4_ordered). The planes lie
-// at least one quantum outside the float node's child boxes, which covers a's rounding (see
-// yrt_qnode.h), so the same boxes are never culled and every query returns the same bits.
-// Empty slots are tested by their child reference.
+// (The same test on the float nodes went with k_trace's float-node traversal, see DESIGN.md.)
 // The quantized node as loaded (14 words).
 struct QNodeData {
   float4 h;   // origin xyz, quantum exponents
@@ -239,14 +167,6 @@ __device__ __forceinline__ QNodeData qnode_load(const GpuQNode* __restrict__ bas
   d.pa = *(const uint4*)(b0 + 32);
   d.pb = *(const uint2*)(b0 + 48);
   return d;
-}
-template <bool ANY>
-__device__ __forceinline__ void box4_qdata(const QNodeData& d, const RayPre& r, int planeOff, float tmax, float t[4],
-                                           int c[4]);
-template <bool ANY>
-__device__ __forceinline__ void box4_quant(const RayPre& r, int planeOff, float tmax, float t[4], int c[4],
-                                           const GpuQNode* __restrict__ base, int nodeIdx) {
-  box4_qdata<ANY>(qnode_load(base, nodeIdx), r, planeOff, tmax, t, c);
 }
 template <bool ANY>
 __device__ __forceinline__ void box4_qdata(const QNodeData& d, const RayPre& r, int planeOff, float tmax, float t[4],
@@ -278,6 +198,11 @@ __device__ __forceinline__ void box4_qdata(const QNodeData& d, const RayPre& r, 
 #undef YRT_QSLAB
 #undef YRT_QB
   const float MISS = __int_as_float(ANY ? 0xff800000 : 0x7f800000);
+  // v_max/v_min written out (+1.5 % on C3, shadow trace 5.84 -> 5.38 ms/launch,
+  // profiles/r02/trace_variants_r02.txt): fmaxf/fminf on the loop-carried tnear / tfar make
+  // the compiler re-quiet (canonicalize) them with an extra v_max every node step (IEEE mode). A signalling
+  // NaN never reaches here (ray records are computed values), and the hardware min/max give
+  // the same result as fmaxf/fminf for every other input.
 #define YRT_CHILD(k, NX, FX, NY, FY, NZ, FZ, CH)                                            \
   do {                                                                                      \
     float nn, ff, a_, b_;                                                                   \
@@ -293,6 +218,11 @@ __device__ __forceinline__ void box4_qdata(const QNodeData& d, const RayPre& r, 
   YRT_CHILD(2, nx23.x, fx23.x, ny23.x, fy23.x, nz23.x, fz23.x, ch.z);
   YRT_CHILD(3, nx23.y, fx23.y, ny23.y, fy23.y, nz23.y, fz23.y, ch.w);
 #undef YRT_CHILD
+}
+template <bool ANY>
+__device__ __forceinline__ void box4_quant(const RayPre& r, int planeOff, float tmax, float t[4], int c[4],
+                                           const GpuQNode* __restrict__ base, int nodeIdx) {
+  box4_qdata<ANY>(qnode_load(base, nodeIdx), r, planeOff, tmax, t, c);
 }
 
 // Sorts the four (t, child) pairs by t ascending (5-comparator network, stable for equal t).
