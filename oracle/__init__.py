@@ -51,6 +51,7 @@ _sig("oracle_count_visits", i32, vp, sz, vp, sz, vp, vp, i32, i32, C.POINTER(C.c
      C.POINTER(C.c_double), vp, sz)
 _sig("oracle_count_visits_q", i32, vp, sz, vp, sz, vp, vp, i32, i32, C.POINTER(C.c_double),
      C.POINTER(C.c_double), vp, sz)
+_sig("oracle_traverse_stats_q", i32, vp, sz, vp, sz, vp, vp, i32, i32, vp, vp, vp, vp, sz)
 _sig("oracle_random_ints", None, i32, i32, vp)
 _sig("oracle_sample_table", i32, i32, i32, i32, i32, i32, C.c_char_p, vp, sz)
 _sig("oracle_pixel_sets", None, i32, i32, i32, vp)
@@ -159,6 +160,27 @@ def count_visits(nodes: np.ndarray, tris: np.ndarray, org4, dir4, any_hit=False,
     if rc != 0:
         raise RuntimeError(f"oracle_count_visits: {_err()}")
     return nv.value, tv.value, hit
+
+
+def traverse_stats(qnodes: np.ndarray, tris: np.ndarray, org4, dir4, any_hit=False, tri_bytes=48):
+    """The kernel-order traversal of the quantized nodes (Device.export_qbvh) per ray: (max_height
+    int32[n], the most stack entries held at any time; first_differs bool[n], the reported triangle
+    is not the first one accepted; hit_under int32[n], the most entries held while the entry that
+    led to the reported triangle waited on the stack; hit float32[n, 4])."""
+    org4 = np.ascontiguousarray(org4, np.float32)
+    dir4 = np.ascontiguousarray(dir4, np.float32)
+    n = org4.shape[0]
+    height = np.zeros(n, np.int32)
+    differs = np.zeros(n, np.int32)
+    under = np.zeros(n, np.int32)
+    hit = np.zeros((n, 4), np.float32)
+    rc = _lib.oracle_traverse_stats_q(qnodes.ctypes.data, qnodes.nbytes // 64, tris.ctypes.data,
+                                      tris.nbytes // tri_bytes, org4.ctypes.data, dir4.ctypes.data, n, int(any_hit),
+                                      height.ctypes.data, differs.ctypes.data, under.ctypes.data, hit.ctypes.data,
+                                      tri_bytes)
+    if rc != 0:
+        raise RuntimeError(f"oracle_traverse_stats_q: {_err()}")
+    return height, differs.astype(bool), under, hit
 
 
 def random_ints(seed, n):

@@ -945,9 +945,19 @@ static inline int tri_test(V3 v0, V3 e1, V3 e2, uint32_t flags, const Ray* r, fl
 static inline int box_hit(const float* lo, const float* hi, const Ray* r, V3 inv, float tmax) {
   float l[3], h[3];
   const float o[3] = {r->org.x, r->org.y, r->org.z}, iv[3] = {inv.x, inv.y, inv.z};
+  const float d[3] = {r->dir.x, r->dir.y, r->dir.z};
   for (int k = 0; k < 3; ++k) {
     l[k] = (lo[k] - o[k]) * iv[k];
     h[k] = (hi[k] - o[k]) * iv[k];
+    /* a direction component that safe_inv clamps (zero, or below 1e-20): the ray stays in its
+     * plane of this axis, so the slab is the whole line when the origin lies within [lo, hi],
+     * planes included, and empty otherwise. The products alone put an origin exactly on a plane
+     * at distance 0 from it and cull the box lying behind that plane (a ray along a box face). */
+    if (!(fabsf(d[k]) > 1e-20f)) {
+      if (!(lo[k] <= o[k] && o[k] <= hi[k])) return 0;
+      l[k] = -INFINITY;
+      h[k] = INFINITY;
+    }
   }
   const float n = fmaxf(fmaxf(fminf(l[0], h[0]), fminf(l[1], h[1])), fmaxf(fminf(l[2], h[2]), r->tnear));
   const float f = fminf(fminf(fmaxf(l[0], h[0]), fmaxf(l[1], h[1])), fminf(fmaxf(l[2], h[2]), tmax));
@@ -2632,23 +2642,41 @@ typedef struct { float v0[4], e1[4], e2[4]; } DTri;
 typedef struct { float origin[3]; uint32_t exps; int32_t child[4]; uint32_t q[6], pad[2]; } QNode;
 static int count_visits_impl(const void* nodes_, const void* qnodes_, const void* tris_, const float* org4,
                              const float* dir4, int n, int anyHit, double* nodeVisits, double* triVisits, float* hit4,
-                             size_t triStride);
+                             size_t triStride, int32_t* maxHeight, int32_t* firstDiffers, int32_t* hitUnder);
 int oracle_count_visits(const void* nodes_, size_t numNodes, const void* tris_, size_t numTris, const float* org4,
                         const float* dir4, int n, int anyHit, double* nodeVisits, double* triVisits, float* hit4,
                         size_t triStride /* bytes per leaf record: 48, or 64 with a stored normal */) {
   (void)numNodes; (void)numTris;
-  return count_visits_impl(nodes_, NULL, tris_, org4, dir4, n, anyHit, nodeVisits, triVisits, hit4, triStride);
+  return count_visits_impl(nodes_, NULL, tris_, org4, dir4, n, anyHit, nodeVisits, triVisits, hit4, triStride, NULL,
+                           NULL, NULL);
 }
 /* the same traversal on the quantized nodes (the any-hit kernel's) */
 int oracle_count_visits_q(const void* qnodes_, size_t numNodes, const void* tris_, size_t numTris, const float* org4,
                           const float* dir4, int n, int anyHit, double* nodeVisits, double* triVisits, float* hit4,
                           size_t triStride) {
   (void)numNodes; (void)numTris;
-  return count_visits_impl(NULL, qnodes_, tris_, org4, dir4, n, anyHit, nodeVisits, triVisits, hit4, triStride);
+  return count_visits_impl(NULL, qnodes_, tris_, org4, dir4, n, anyHit, nodeVisits, triVisits, hit4, triStride, NULL,
+                           NULL, NULL);
+}
+/* The quantized-node traversal again, reporting per ray what the ray-query kernel's stack and
+ * tie rule go through: maxHeight[i], the most entries on the traversal stack at any time (after
+ * a node's pushes; the kernel parks one leaf and pops ahead, so its own height differs by at
+ * most one entry), and firstDiffers[i], 1 when the triangle finally reported is not the first
+ * one the traversal accepted (a later, closer or tie-winning triangle replaced it), and
+ * hitUnder[i], the most entries the stack held while the entry that led to the reported triangle
+ * waited on it (0: found on the first descent from the root): at more than the kernel's ring size
+ * the reported hit went through the spill to global memory and back. */
+int oracle_traverse_stats_q(const void* qnodes_, size_t numNodes, const void* tris_, size_t numTris, const float* org4,
+                            const float* dir4, int n, int anyHit, int32_t* maxHeight, int32_t* firstDiffers,
+                            int32_t* hitUnder, float* hit4, size_t triStride) {
+  (void)numNodes; (void)numTris;
+  double nv, tv;
+  return count_visits_impl(NULL, qnodes_, tris_, org4, dir4, n, anyHit, &nv, &tv, hit4, triStride, maxHeight,
+                           firstDiffers, hitUnder);
 }
 static int count_visits_impl(const void* nodes_, const void* qnodes_, const void* tris_, const float* org4,
                              const float* dir4, int n, int anyHit, double* nodeVisits, double* triVisits, float* hit4,
-                             size_t triStride) {
+                             size_t triStride, int32_t* maxHeight, int32_t* firstDiffers, int32_t* hitUnder) {
   const DNode* nodes = (const DNode*)nodes_;
   const QNode* qnodes = (const QNode*)qnodes_;
   const char* trisBytes = (const char*)tris_;
@@ -2658,6 +2686,9 @@ static int count_visits_impl(const void* nodes_, const void* qnodes_, const void
     Ray r = {v3(org4[4 * i], org4[4 * i + 1], org4[4 * i + 2]), v3(dir4[4 * i], dir4[4 * i + 1], dir4[4 * i + 2]),
              org4[4 * i + 3], dir4[4 * i + 3]};
     Hit best = {r.tfar, 0, 0, -1};
+    /* peak[k]: the greatest height since entry k was pushed (handed down at every pop);
+     * curPeak: that of the entry the current descent was popped from */
+    int maxSp = 0, firstTri = -1, curPeak = 0, bestPeak = 0, peak[128];
     if (r.tfar >= r.tnear) {
       const V3 inv = v3(safe_inv(r.dir.x), safe_inv(r.dir.y), safe_inv(r.dir.z));
       const float o[3] = {r.org.x, r.org.y, r.org.z}, iv[3] = {inv.x, inv.y, inv.z};
@@ -2722,9 +2753,10 @@ static int count_visits_impl(const void* nodes_, const void* qnodes_, const void
               }
             }
           }
-          if (t[3] < INF) stack[sp++] = c[3];
-          if (t[2] < INF) stack[sp++] = c[2];
-          if (t[1] < INF) stack[sp++] = c[1];
+          if (t[3] < INF) { peak[sp] = sp + 1; stack[sp++] = c[3]; }
+          if (t[2] < INF) { peak[sp] = sp + 1; stack[sp++] = c[2]; }
+          if (t[1] < INF) { peak[sp] = sp + 1; stack[sp++] = c[1]; }
+          if (sp > maxSp) maxSp = sp;
           if (t[0] < INF) {
             cur = c[0];
             continue;
@@ -2742,13 +2774,15 @@ static int count_visits_impl(const void* nodes_, const void* qnodes_, const void
             int ok = tri_test(v3(t->v0[0], t->v0[1], t->v0[2]), v3(t->e1[0], t->e1[1], t->e1[2]),
                               v3(t->e2[0], t->e2[1], t->e2[2]), fl, &r, anyHit ? r.tfar : best.t, &tt, &u, &v);
             if (anyHit) {
-              if (ok) { best.t = tt; best.u = u; best.v = v; best.tri = gid; done = 1; break; }
+              if (ok) { best.t = tt; best.u = u; best.v = v; best.tri = gid; firstTri = gid; bestPeak = curPeak; done = 1; break; }
             } else {
               if (!ok && best.tri >= 0 && tt == best.t && gid < best.tri) {
                 float t2, u2, v2;
                 ok = tri_test(v3(t->v0[0], t->v0[1], t->v0[2]), v3(t->e1[0], t->e1[1], t->e1[2]),
                               v3(t->e2[0], t->e2[1], t->e2[2]), fl, &r, r.tfar, &t2, &u2, &v2);
               }
+              if (ok && firstTri < 0) firstTri = gid;
+              if (ok) bestPeak = curPeak;
               if (ok) { best.t = tt; best.u = u; best.v = v; best.tri = gid; }
             }
           }
@@ -2756,12 +2790,17 @@ static int count_visits_impl(const void* nodes_, const void* qnodes_, const void
         }
         if (sp == 0) break;
         cur = stack[--sp];
+        curPeak = peak[sp];
+        if (sp > 0 && peak[sp - 1] < curPeak) peak[sp - 1] = curPeak;
       }
     }
     if (hit4) {
       hit4[4 * i] = best.t; hit4[4 * i + 1] = best.u; hit4[4 * i + 2] = best.v;
       memcpy(&hit4[4 * i + 3], &best.tri, 4);
     }
+    if (maxHeight) maxHeight[i] = maxSp;
+    if (firstDiffers) firstDiffers[i] = best.tri >= 0 && firstTri != best.tri;
+    if (hitUnder) hitUnder[i] = best.tri >= 0 ? bestPeak : 0;
   }
   *nodeVisits = nv;
   *triVisits = tv;

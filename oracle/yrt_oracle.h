@@ -87,6 +87,12 @@ int oracle_count_visits(const void* nodes, size_t numNodes, const void* tris, si
 int oracle_count_visits_q(const void* qnodes, size_t numNodes, const void* tris, size_t numTris, const float* org4,
                           const float* dir4, int n, int anyHit, double* nodeVisits, double* triVisits, float* hit4,
                           size_t triStride);
+/* the quantized-node traversal with, per ray, maxHeight[i] = most entries on the traversal stack
+ * at any time, firstDiffers[i] = 1 when the reported triangle is not the first one accepted, and
+ * hitUnder[i] = most entries held while the entry leading to the reported triangle waited */
+int oracle_traverse_stats_q(const void* qnodes, size_t numNodes, const void* tris, size_t numTris, const float* org4,
+                            const float* dir4, int n, int anyHit, int32_t* maxHeight, int32_t* firstDiffers,
+                            int32_t* hitUnder, float* hit4, size_t triStride);
 
 /* Reference Random (common/math/random.h): n draws of getInt() after setSeed(seed). */
 void oracle_random_ints(int seed, int n, int32_t* out);

@@ -172,7 +172,7 @@ def test_c3_standin_parity(gpu_device):
 
 
 def test_c3_full_size_band_parity(gpu_device):
-    """C3 at its BASELINE size (2048^2, 64 spp, depth 10, 64 M-path batches over two lanes):
+    """C3 at its BASELINE size (2048^2, 64 spp, depth 10, 64 M-path batches over three lanes):
     the GPU frame against the oracle on a centred band of 64 full rows (same frame blob)."""
     s = _session(gpu_device, c3_args(2048, 64))
     info = s.info()

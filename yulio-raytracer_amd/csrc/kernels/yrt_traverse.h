@@ -101,13 +101,31 @@ __device__ __forceinline__ void box4(const GpuNode* __restrict__ np, const RayPr
   const int4 ch = *(const int4*)(q + 6);
   const f2 ox = {r.org.x, r.org.x}, oy = {r.org.y, r.org.y}, oz = {r.org.z, r.org.z};
   const f2 ix = {r.inv.x, r.inv.x}, iy = {r.inv.y, r.inv.y}, iz = {r.inv.z, r.inv.z};
-  const f2 lx01 = (f2{lx.x, lx.y} - ox) * ix, lx23 = (f2{lx.z, lx.w} - ox) * ix;
-  const f2 hx01 = (f2{hx.x, hx.y} - ox) * ix, hx23 = (f2{hx.z, hx.w} - ox) * ix;
-  const f2 ly01 = (f2{ly.x, ly.y} - oy) * iy, ly23 = (f2{ly.z, ly.w} - oy) * iy;
-  const f2 hy01 = (f2{hy.x, hy.y} - oy) * iy, hy23 = (f2{hy.z, hy.w} - oy) * iy;
-  const f2 lz01 = (f2{lz.x, lz.y} - oz) * iz, lz23 = (f2{lz.z, lz.w} - oz) * iz;
-  const f2 hz01 = (f2{hz.x, hz.y} - oz) * iz, hz23 = (f2{hz.z, hz.w} - oz) * iz;
+  f2 lx01 = (f2{lx.x, lx.y} - ox) * ix, lx23 = (f2{lx.z, lx.w} - ox) * ix;
+  f2 hx01 = (f2{hx.x, hx.y} - ox) * ix, hx23 = (f2{hx.z, hx.w} - ox) * ix;
+  f2 ly01 = (f2{ly.x, ly.y} - oy) * iy, ly23 = (f2{ly.z, ly.w} - oy) * iy;
+  f2 hy01 = (f2{hy.x, hy.y} - oy) * iy, hy23 = (f2{hy.z, hy.w} - oy) * iy;
+  f2 lz01 = (f2{lz.x, lz.y} - oz) * iz, lz23 = (f2{lz.z, lz.w} - oz) * iz;
+  f2 hz01 = (f2{hz.x, hz.y} - oz) * iz, hz23 = (f2{hz.z, hz.w} - oz) * iz;
   const float INF = __int_as_float(0x7f800000);
+  // A direction component that safe_inv clamps (zero, or below 1e-20): the ray stays in its plane
+  // of that axis, so the slab is the whole line when the origin lies within [lo, hi], planes
+  // included, and empty otherwise (near = far = +INF: missed whenever another axis or tmax bounds
+  // the exit; a ray with all three components clamped hits no triangle anyway). The products
+  // alone put an origin exactly on a plane at distance 0 from it and cull the box lying behind
+  // that plane (a ray along a box face); the oracle's box_hit does the same.
+#define YRT_FLAT_IN(LO_, O, HI_) (((LO_) <= (O) && (O) <= (HI_)) ? -INF : INF)
+#define YRT_FLAT_AXIS(D, O, LO, HI, L01, L23, H01, H23)               \
+  if (!(fabsf(D) > 1e-20f)) {                                         \
+    L01 = f2{YRT_FLAT_IN(LO.x, O, HI.x), YRT_FLAT_IN(LO.y, O, HI.y)}; \
+    L23 = f2{YRT_FLAT_IN(LO.z, O, HI.z), YRT_FLAT_IN(LO.w, O, HI.w)}; \
+    H01 = H23 = f2{INF, INF};                                         \
+  }
+  YRT_FLAT_AXIS(r.dir.x, r.org.x, lx, hx, lx01, lx23, hx01, hx23)
+  YRT_FLAT_AXIS(r.dir.y, r.org.y, ly, hy, ly01, ly23, hy01, hy23)
+  YRT_FLAT_AXIS(r.dir.z, r.org.z, lz, hz, lz01, lz23, hz01, hz23)
+#undef YRT_FLAT_AXIS
+#undef YRT_FLAT_IN
 #define YRT_CHILD(k, LX, HX, LY, HY, LZ, HZ, CH)                                                          \
   do {                                                                                                    \
     const float nn = fmaxf(fmaxf(fminf(LX, HX), fminf(LY, HY)), fmaxf(fminf(LZ, HZ), r.tnear));          \
