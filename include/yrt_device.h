@@ -131,6 +131,42 @@ YRT_API int yrtSwapBuffers(YRTDevice dev, YRTHandle framebuffer);
  * the camera ray through image-plane point (x, y) in [0,1]^2. Returns 1 hit, 0 miss, <0 error. */
 YRT_API int yrtPick(YRTDevice dev, YRTHandle camera, float x, float y, YRTHandle scene, float* px, float* py,
                     float* pz);
+/* ---- denoise: first-hit guide buffers and an edge-avoiding a-trous filter ---- */
+/* yrtRenderGuides: for pixel (x, y) of a width x height view, rtPick's camera ray through the
+ * image-plane point ((x + .5) / width, (y + .5) / height) (time 0 in moving scenes):
+ * pos4Host[4 i] = (hit point, t), nrm4Host[4 i] = (shading normal turned towards the viewer, 1),
+ * i = y * width + x; a miss gives (0, 0, 0, +inf) and (0, 0, 0, 0). width * height * 4 floats each. */
+YRT_API int yrtRenderGuides(YRTDevice dev, YRTHandle camera, YRTHandle scene, int width, int height,
+                            float* pos4Host, float* nrm4Host);
+/* size = sizeof(YRTDenoiseParams) of the caller's build, checked: a shorter struct is read up to
+ * its size and the remaining fields take their defaults; below sizeof(size) is an error.
+ * iterations: filter passes, step 2^i (0: the call writes nothing). sigmaColor: colour weight
+ * exp(-|dc|^2 / (sigmaColor 2^-i)^2), <= 0 turns it off. sigmaNormal: exponent of
+ * max(0, n_p . n_q). sigmaPosition: plane-distance weight exp(-|n_p . (x_q - x_p)| /
+ * (sigmaPosition t_p)). Defaults: 5, 1, 64, 0.02 (yrtDenoiseDefaults). */
+typedef struct YRTDenoiseParams {
+  uint32_t size;
+  int iterations;
+  float sigmaColor, sigmaNormal, sigmaPosition;
+} YRTDenoiseParams;
+/* Fills the fields that fit into p->size (set by the caller) with the library's defaults. */
+YRT_API int yrtDenoiseDefaults(YRTDenoiseParams* p);
+/* Filters the framebuffer's current buffer in place, guided by the first hits seen through
+ * `camera` (the camera the frame was rendered with; a cube face's own). The filter input is the
+ * frame as it stands — tone mapped, 8-bit channels as byte / 255 — and the result is stored in
+ * the framebuffer's own format; alpha channels, RGB8 row padding and pixels whose camera ray
+ * leaves the scene are not written. The frame is filtered where it lives: an RGB8 or
+ * RGB_FLOAT32 frame that no rtMapFrameBuffer has read yet is filtered in HBM (and read back
+ * filtered by the next map); any other is uploaded from the host pixels, filtered and written
+ * back to them. Runs on the device's first GPU, after the gather of a multi-GPU render; under
+ * process tile shards (yrtSetTileShard / yrtSetShardComm) call it on the rank that holds the
+ * gathered frame (rank 0): it filters whatever the framebuffer holds. p = NULL: defaults. */
+YRT_API int yrtDenoiseFrameBuffer(YRTDevice dev, YRTHandle camera, YRTHandle scene, YRTHandle framebuffer,
+                                  const YRTDenoiseParams* p);
+/* With yrtSetKernelTiming on: HIP-event times, in ms, of the kernels of the last guide pass
+ * (yrtRenderGuides, or the one inside yrtDenoiseFrameBuffer) and of the last filter (its load and
+ * iterations, without the guide pass and any host copy). Either pointer may be NULL. */
+YRT_API int yrtGetDenoiseTimes(YRTDevice dev, float* msGuides, float* msFilter);
 /* Renderer status callback (device.h:335-347): state 0 Inactive, 1 Rendering, 2 Done. */
 typedef void (*YRTStatusCallback)(int state, float progress, void* user);
 YRT_API int yrtSetStatusCallback(YRTDevice dev, YRTHandle renderer, YRTStatusCallback cb, void* user);

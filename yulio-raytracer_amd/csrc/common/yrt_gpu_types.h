@@ -181,6 +181,8 @@ struct GpuRenderParams {
   // radiance of a camera ray that misses, for the fused depth 0 (PrimaryRays): the sum over the
   // environment lights of 1 * L, as k_shade's depth-0 miss branch adds it (ambient lights only)
   float missL[4];
+  // DefaultToneMapper's vignette (k_resolve_pixels); appended: the offsets above are k_shade's
+  int32_t vignetting, padV[3];
 };
 
 // Camera (cameras/pinholecamera.h:15-21, cameras/StereoCubeCamera.h:16-65).

@@ -92,6 +92,9 @@ struct GpuCtx {
   Lane lanes[kMaxLanes];
   int numLanes = kDefaultLanes;
   DevBuf dRp, dCam, dPixelSets, dAccu, dCount, dSpill, dSlab, dDirect;
+  // denoise (yrtRenderGuides / yrtDenoiseFrameBuffer): the guide frames, the filter's two
+  // ping-pong float4 frames and the upload of a frame that lives in host pixels
+  DevBuf dGuidePos, dGuideNrm, dFilter[2], dFilterFb;
   // The frames a job renders into (float RGB and RGB8 rows, frame-major). On the primary
   // device a job's framebuffers keep a reference to their block until rtMapFrameBuffer reads
   // them back, so the next job renders into the spare (or a fresh) block meanwhile.
@@ -354,6 +357,37 @@ class Device {
   }
   void intersect(SceneObj& S, const float* org4, const float* dir4, uint32_t n, float* hit4, int32_t* occ,
                  hipStream_t st);
+  // the first-hit guide frames of a W x H view of C in ctx[0]'s dGuidePos / dGuideNrm (enqueued
+  // on the primary stream)
+  void guides(CameraObj& C, SceneObj& S, int W, int H, const char* what);
+  // yrtSetKernelTiming: HIP-event times of the last guide pass and the last filter (its load and
+  // iterations), yrtGetDenoiseTimes; the events are read once the stream has been synchronized
+  struct EvPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    void reset() {
+      if (a) (void)hipEventDestroy(a);
+      if (b) (void)hipEventDestroy(b);
+      a = b = nullptr;
+    }
+    void start(bool on, hipStream_t st) {
+      reset();  // a call that threw before its read
+      if (!on) return;
+      HIP_CHECK(hipEventCreate(&a));
+      HIP_CHECK(hipEventCreate(&b));
+      HIP_CHECK(hipEventRecord(a, st));
+    }
+    void stop(hipStream_t st) {
+      if (b) HIP_CHECK(hipEventRecord(b, st));
+    }
+    // after the stream's synchronize; leaves ms as it is when timing is off
+    void read(float& ms) {
+      if (b) HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+      reset();
+    }
+  };
+  EvPair evGuides, evFilter;
+  float msGuides = 0.f, msFilter = 0.f;
+  void denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDenoiseParams& p);
 };
 
 // ---------------------------------------------------------------- rendering
@@ -544,6 +578,88 @@ void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& 
   status(R, 2, 1.f);
 }
 
+// ---------------------------------------------------------------- denoise
+void Device::guides(CameraObj& C, SceneObj& S, int W, int H, const char* what) {
+  if (!S.gpu) throw std::runtime_error(std::string(what) + ": scene not committed");
+  if (S.gpu->device != hipDevice) throw std::runtime_error(std::string(what) + ": scene committed on another HIP device");
+  // one thread per pixel in 64-lane blocks: the grid stays far inside 2^31 blocks
+  if ((long long)W * H > (1ll << 30)) throw std::runtime_error(std::string(what) + ": more than 2^30 pixels");
+  HIP_CHECK(hipSetDevice(hipDevice));
+  GpuCtx& g = *ctx[0];
+  const size_t bytes = (size_t)W * H * sizeof(float4);
+  g.dCam.alloc(sizeof(GpuCamera));
+  g.dGuidePos.alloc(bytes);
+  g.dGuideNrm.alloc(bytes);
+  HIP_CHECK(hipMemcpyAsync(g.dCam.p, &C.cam, sizeof(GpuCamera), hipMemcpyHostToDevice, stream));
+  evGuides.start(kernelTiming, stream);
+  launch_guides(S.gpu->view, g.dCam.as<GpuCamera>(), W, H, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(), stream);
+  evGuides.stop(stream);
+  HIP_CHECK(hipGetLastError());
+}
+
+// yrtDenoiseFrameBuffer: guides, c_0 = the frame as it stands, `iterations` a-trous passes
+// ping-ponging between two float4 frames, the last one storing into the frame's own format.
+// An RGB8 / RGB_FLOAT32 frame still in ctx[0]'s frame block is filtered there (the block holds
+// exactly those layouts; the next rtMapFrameBuffer reads the filtered frame back). The RGBA
+// formats exist on the host only (fb_read_back converts the block's RGB floats), so such a frame
+// is read back first and, like any frame already mapped or rendered into user pointers,
+// uploaded from the host pixels, filtered and copied back into them.
+void Device::denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDenoiseParams& p) {
+  if (!S.gpu) throw std::runtime_error("yrtDenoiseFrameBuffer: scene not committed");
+  if (p.iterations == 0) return;
+  const int W = F.width, H = F.height, id = F.cur;
+  if (W < 1 || H < 1) return;
+  guides(C, S, W, H, "yrtDenoiseFrameBuffer");
+  GpuCtx& g = *ctx[0];
+  const bool bytes8 = F.format == FB_RGB8 || F.format == FB_RGBA8;
+  const bool rgba = F.format == FB_RGBA8 || F.format == FB_RGBA_FLOAT32;
+  FrameIO io;
+  io.width = W;
+  io.height = H;
+  io.pixStride = rgba ? 4 : 3;
+  io.bytes = bytes8 ? 1 : 0;
+  io.rowStride = bytes8 ? F.stride : F.stride / sizeof(float);
+  const bool pending = id < (int)F.pending.size() && F.pending[id].keep;
+  const bool inBlock = pending && !rgba && F.pending[id].hipDevice == hipDevice;
+  const size_t fbBytes = F.stride * (size_t)H;
+  if (inBlock) {
+    io.pixels = const_cast<void*>(F.pending[id].src);
+  } else {
+    if (pending) fb_read_back(F, id);
+    HIP_CHECK(hipSetDevice(hipDevice));
+    g.dFilterFb.alloc(fbBytes);
+    HIP_CHECK(hipMemcpyAsync(g.dFilterFb.p, F.buffer(id), fbBytes, hipMemcpyHostToDevice, stream));
+    io.pixels = g.dFilterFb.p;
+  }
+  const size_t frameBytes = (size_t)W * H * sizeof(float4);
+  g.dFilter[0].alloc(frameBytes);
+  if (p.iterations > 1) g.dFilter[1].alloc(frameBytes);
+  evFilter.start(kernelTiming, stream);
+  launch_atrous_load(io, g.dFilter[0].as<float4>(), stream);
+  AtrousParams ap;
+  memset(&ap, 0, sizeof(ap));
+  ap.width = W;
+  ap.height = H;
+  ap.sigmaNormal = p.sigmaNormal;
+  ap.sigmaPosition = p.sigmaPosition;
+  const FrameIO none{nullptr, 0, W, H, 0, 0};
+  for (int i = 0; i < p.iterations; ++i) {
+    const bool last = i + 1 == p.iterations;
+    ap.step = 1 << i;
+    // sigmaColor_i = sigmaColor 2^-i (Dammertz et al.): the colour weight tightens as the taps spread
+    const float sc = p.sigmaColor > 0.f ? p.sigmaColor / (float)(1 << i) : 0.f;
+    ap.rcpSigmaColor2 = sc > 0.f ? 1.0f / (sc * sc) : 0.f;
+    launch_atrous(ap, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(), g.dFilter[i & 1].as<float4>(),
+                  last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(), last ? io : none, stream);
+  }
+  evFilter.stop(stream);
+  HIP_CHECK(hipGetLastError());
+  if (!inBlock) HIP_CHECK(hipMemcpyAsync(F.buffer(id), g.dFilterFb.p, fbBytes, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  evGuides.read(msGuides);
+  evFilter.read(msFilter);
+}
+
 // Renders the tiles of shard (index, count) of the frame into g's full-size buffers (the other
 // tiles' pixels are left zero when count > 1).
 void Device::render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vector<CameraObj*>& C,
@@ -565,6 +681,7 @@ void Device::render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vec
   rp.rcpHeight = rcpf_(float(H));
   rp.gamma = T.gamma;
   rp.rcpGamma = rcpf_(T.gamma);
+  rp.vignetting = T.vignetting ? 1 : 0;
   rp.frameSeed = frameSeed;
   rp.maxDepth = R.maxDepth;
   rp.rrDepth = R.rrDepth;
@@ -1854,6 +1971,83 @@ int yrtPick(YRTDevice dev, YRTHandle camera, float x, float y, YRTHandle scene, 
   *py = r.y;
   *pz = r.z;
   return __builtin_bit_cast(int, r.w) >= 0 ? 1 : 0;
+  DEV_END(-1)
+}
+
+// The library's YRTDenoiseParams: the defaults overlaid by the fields the caller's struct holds.
+// sigmaColor 1: the lowest mean squared error against a 1024-spp frame, summed over C1 and C2,
+// among 0.25, 0.5, 1, 2 and off.
+static YRTDenoiseParams denoise_params(const YRTDenoiseParams* p) {
+  YRTDenoiseParams d;
+  d.size = (uint32_t)sizeof(YRTDenoiseParams);
+  d.iterations = 5;
+  d.sigmaColor = 1.0f;
+  d.sigmaNormal = 64.f;
+  d.sigmaPosition = 0.02f;
+  if (!p) return d;
+  if (p->size < sizeof(uint32_t)) throw std::runtime_error("YRTDenoiseParams: size is smaller than the size field");
+  const size_t n = p->size;
+#define YRT_DN_FIELD(f) \
+  if (n >= offsetof(YRTDenoiseParams, f) + sizeof(d.f)) d.f = p->f
+  YRT_DN_FIELD(iterations);
+  YRT_DN_FIELD(sigmaColor);
+  YRT_DN_FIELD(sigmaNormal);
+  YRT_DN_FIELD(sigmaPosition);
+#undef YRT_DN_FIELD
+  if (d.iterations < 0 || d.iterations > 16) throw std::runtime_error("YRTDenoiseParams: iterations outside 0..16");
+  if (!(d.sigmaNormal >= 0.f) || !(d.sigmaPosition > 0.f) || d.sigmaColor != d.sigmaColor)
+    throw std::runtime_error("YRTDenoiseParams: sigmaNormal >= 0 and sigmaPosition > 0 are required");
+  return d;
+}
+
+int yrtDenoiseDefaults(YRTDenoiseParams* p) {
+  if (!p || p->size < sizeof(uint32_t)) return -1;
+  const YRTDenoiseParams d = denoise_params(nullptr);
+  memcpy((char*)p + sizeof(uint32_t), (const char*)&d + sizeof(uint32_t),
+         std::min<size_t>(p->size, sizeof(d)) - sizeof(uint32_t));
+  return 0;
+}
+
+int yrtRenderGuides(YRTDevice dev, YRTHandle camera, YRTHandle scene, int width, int height, float* pos4Host,
+                    float* nrm4Host) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  if (!D.gpu) throw std::runtime_error("yrtRenderGuides: host-only device (created with parms \"host\")");
+  auto C = D.get<CameraObj>(camera, "camera");
+  auto S = D.get<SceneObj>(scene, "scene");
+  if (!C || !S || !pos4Host || !nrm4Host) throw std::runtime_error("yrtRenderGuides: null handle or pointer");
+  if (width < 1 || height < 1) throw std::runtime_error("yrtRenderGuides: empty frame");
+  D.guides(*C, *S, width, height, "yrtRenderGuides");
+  GpuCtx& g = *D.ctx[0];
+  const size_t bytes = (size_t)width * height * sizeof(float4);
+  HIP_CHECK(hipMemcpyAsync(pos4Host, g.dGuidePos.p, bytes, hipMemcpyDeviceToHost, D.stream));
+  HIP_CHECK(hipMemcpyAsync(nrm4Host, g.dGuideNrm.p, bytes, hipMemcpyDeviceToHost, D.stream));
+  HIP_CHECK(hipStreamSynchronize(D.stream));
+  D.evGuides.read(D.msGuides);
+  return 0;
+  DEV_END(-1)
+}
+
+int yrtDenoiseFrameBuffer(YRTDevice dev, YRTHandle camera, YRTHandle scene, YRTHandle framebuffer,
+                          const YRTDenoiseParams* p) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  const YRTDenoiseParams dp = denoise_params(p);
+  if (!D.gpu) throw std::runtime_error("yrtDenoiseFrameBuffer: host-only device (created with parms \"host\")");
+  auto C = D.get<CameraObj>(camera, "camera");
+  auto S = D.get<SceneObj>(scene, "scene");
+  auto F = D.get<FrameBufferObj>(framebuffer, "framebuffer");
+  if (!C || !S || !F) throw std::runtime_error("yrtDenoiseFrameBuffer: null handle");
+  D.denoise(*C, *S, *F, dp);
+  return 0;
+  DEV_END(-1)
+}
+
+int yrtGetDenoiseTimes(YRTDevice dev, float* msGuides, float* msFilter) {
+  DEV_GUARD(dev, -1)
+  if (msGuides) *msGuides = dev->d->msGuides;
+  if (msFilter) *msFilter = dev->d->msFilter;
+  return 0;
   DEV_END(-1)
 }
 

@@ -570,7 +570,6 @@ void ToneMapperObj::commit() {
   // tonemappers/defaulttonemapper.h:15-20
   gamma = parms.getFloat("gamma", 1.0f);
   vignetting = parms.getBool("vignetting", false);
-  if (vignetting) throw std::runtime_error("vignetting is not supported by the MI355X device");
 }
 
 void RendererObj::commit() {

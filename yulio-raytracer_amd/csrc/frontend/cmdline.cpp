@@ -5,6 +5,7 @@
 //   parseCommandLine           :974-1403
 //   createCamera / createScene :309-345
 //   outputMode                 :508-905 (mono and non-FPR stereo branches)
+#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
 #include <dlfcn.h>
@@ -307,6 +308,9 @@ void RtState::parseCommandLine(const std::vector<std::string>& tokens, const std
       vignetting = cin.getInt() != 0;
       check(dev, yrtSetBool1(dev, tonemapper, "vignetting", vignetting), "rtSetBool1");
       check(dev, yrtCommit(dev, tonemapper), "rtCommit(tonemapper)");
+    } else if (tag == "-denoise") {
+      denoise = cin.getInt();
+      if (denoise < 0) throw std::runtime_error("-denoise: the iteration count must not be negative");
     } else if (tag == "-depth") {
       depth = cin.getInt();
       check(dev, yrtSetInt1(dev, renderer, "maxDepth", depth), "rtSetInt1");
@@ -582,7 +586,16 @@ void RtState::renderFprFace(size_t i) {
     check(dev, yrtCommit(dev, cam), "rtCommit(camera)");
   }
   check(dev, yrtRenderFrame(dev, renderer, cam, sc, tonemapper, frameBuffer, 0), "rtRenderFrame");
+  denoiseFrame(cam, sc, frameBuffer);
   for (int j = 0; j < numBuffers; ++j) check(dev, yrtSwapBuffers(dev, frameBuffer), "rtSwapBuffers");
+}
+
+void RtState::denoiseFrame(YRTHandle cam, YRTHandle sc, YRTHandle fb) {
+  if (denoise <= 0) return;
+  YRTDenoiseParams p;
+  p.size = (uint32_t)(offsetof(YRTDenoiseParams, iterations) + sizeof(p.iterations));  // the weights: defaults
+  p.iterations = denoise;
+  check(dev, yrtDenoiseFrameBuffer(dev, cam, sc, fb, &p), "yrtDenoiseFrameBuffer");
 }
 
 void RtState::renderCube(const std::vector<YRTHandle>& cams) {
@@ -599,6 +612,7 @@ void RtState::renderCube(const std::vector<YRTHandle>& cams) {
   YRTHandle sc = createScene();
   check(dev, yrtRenderFrames(dev, renderer, cams.data(), (int)cams.size(), sc, tonemapper, cubeFrameBuffers.data(), 0),
         "rtRenderFrames");
+  for (size_t k = 0; k < cams.size(); ++k) denoiseFrame(cams[k], sc, cubeFrameBuffers[k]);
 }
 
 std::vector<uint8_t> RtState::cubeFace(int k) {
@@ -748,6 +762,7 @@ void RtState::outputMode(const std::string& fileName, std::vector<uint8_t>* outI
         if (onStage) onStage(i, 12);
         YRTHandle cam = createCamera(i);
         check(dev, yrtRenderFrame(dev, renderer, cam, sc, tonemapper, frameBuffer, 0), "rtRenderFrame");
+        denoiseFrame(cam, sc, frameBuffer);
         for (int j = 0; j < numBuffers; ++j) check(dev, yrtSwapBuffers(dev, frameBuffer), "rtSwapBuffers");
         const uint8_t* p = (const uint8_t*)yrtMapFrameBuffer(dev, frameBuffer, -1);
         faces[i].assign(p, p + stride * height);
@@ -778,8 +793,10 @@ void RtState::outputMode(const std::string& fileName, std::vector<uint8_t>* outI
     YRTHandle cam = createCamera(-1);
     check(dev, yrtSetInt1(dev, renderer, "showprogress", 1), "rtSetInt1");
     check(dev, yrtCommit(dev, renderer), "rtCommit(renderer)");
-    for (int i = 0; i < numFrames; i++)
+    for (int i = 0; i < numFrames; i++) {
       check(dev, yrtRenderFrame(dev, renderer, cam, sc, tonemapper, frameBuffer, 0), "rtRenderFrame");
+      denoiseFrame(cam, sc, frameBuffer);
+    }
     for (int i = 0; i < numBuffers; i++) check(dev, yrtSwapBuffers(dev, frameBuffer), "rtSwapBuffers");
     const uint8_t* p = (const uint8_t*)yrtMapFrameBuffer(dev, frameBuffer, -1);
     if (!fileName.empty()) {

@@ -103,6 +103,7 @@ struct RtState {
   int depth = -1, spp = 1, numBuffers = 1;
   float gamma = 1.0f;
   bool vignetting = false;
+  int denoise = 0;  // -denoise <iterations>: a-trous passes over every rendered frame (0: off)
   int width = 512, height = 512;
   std::string format = "RGB8";
   std::string outFileName;
@@ -124,6 +125,9 @@ struct RtState {
   void parseCommandLine(const std::vector<std::string>& tokens, const std::string& path);
   YRTHandle createCamera(int face);
   YRTHandle createScene();
+  // -denoise: filters the frame just rendered into fb through cam (yrtDenoiseFrameBuffer with the
+  // library's default weights), before it is read, watermarked or assembled into a strip
+  void denoiseFrame(YRTHandle cam, YRTHandle sc, YRTHandle fb);
   void outputMode(const std::string& file, std::vector<uint8_t>* outImage = nullptr);
   // FPR branch of outputMode (renderer.cpp:519-737): per camera view, update faceCamera
   // primitives, render the 12 faces, store <dir>/<name>_<camera>.jpg

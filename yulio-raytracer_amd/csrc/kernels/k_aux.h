@@ -4,6 +4,7 @@
 
 #include "yrt_camera.h"
 #include "yrt_shade.h"
+#include "yrt_surface.h"
 #include "yrt_traverse.h"
 
 namespace yrt {
@@ -172,6 +173,127 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) void k_pick(SceneView sv, const Gp
   const Hit h = traverse<false>(sv.nodes, sv.tris, r, stack + threadIdx.x);
   const V3 p = org + h.t * dir;
   out[0] = make_float4(p.x, p.y, p.z, __int_as_float(h.tri));
+}
+
+// ---------------------------------------------------------------- denoise: guides + filter
+// First-hit guide buffers (yrtRenderGuides, the denoiser's input): pixel (x, y) traces k_pick's
+// ray through the image-plane point ((x + .5) / W, (y + .5) / H) (IEEE divisions: the float a
+// caller computes for rtPick), time 0, and stores pos4 = (org + t dir, t) and nrm4 = (Ns, 1)
+// with postIntersect's shading normal turned towards the viewer; a miss stores (0, 0, 0, inf)
+// and 0.
+__global__ __launch_bounds__(YRT_TRACE_BLOCK) void k_guides(SceneView sv, const GpuCamera* camp, int width, int height,
+                                                            float4* __restrict__ pos4, float4* __restrict__ nrm4) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)width * height) return;
+  const int y = (int)(i / width), x = (int)(i - (long long)y * width);
+  V3 org, dir;
+  camera_ray(*camp, (float(x) + 0.5f) / float(width), (float(y) + 0.5f) / float(height), org, dir);
+  RayPre r;
+  r.org = org;
+  r.dir = dir;
+  r.inv = v3(safe_inv(dir.x), safe_inv(dir.y), safe_inv(dir.z));
+  r.tnear = 0.f;
+  r.tfar = __int_as_float(0x7f800000);
+  const Hit h = traverse<false>(sv.nodes, sv.tris, r, nullptr);
+  if (h.tri < 0) {
+    pos4[i] = make_float4(0.f, 0.f, 0.f, __int_as_float(0x7f800000));
+    nrm4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  DG dg;
+  post_intersect_g(sv, sv.geoms[sv.triGeom[h.tri]], org, dir, h.t, h.u, h.v, h.tri, dg, false);
+  V3 n = dg.Ns;
+  if (dot(n, dir) > 0.f) n = -n;
+  pos4[i] = make_float4(dg.P.x, dg.P.y, dg.P.z, h.t);
+  nrm4[i] = make_float4(n.x, n.y, n.z, 1.f);
+}
+
+// A framebuffer as the filter reads and writes it: float or 8-bit channels, 3 or 4 per pixel,
+// rows rowStride channels apart (RGB8 rows are padded to 4 bytes).
+__device__ __forceinline__ size_t fb_channel(const FrameIO& io, int x, int y) {
+  return (size_t)y * io.rowStride + (size_t)x * io.pixStride;
+}
+
+// c_0 of the filter: the framebuffer's pixels as float4 (8-bit channels as byte / 255)
+__global__ __launch_bounds__(YRT_BLOCK) void k_atrous_load(FrameIO io, float4* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)io.width * io.height) return;
+  const int y = (int)(i / io.width), x = (int)(i - (long long)y * io.width);
+  const size_t o = fb_channel(io, x, y);
+  float4 c;
+  if (io.bytes) {
+    const uint8_t* p = (const uint8_t*)io.pixels + o;
+    c = make_float4(float(p[0]) / 255.0f, float(p[1]) / 255.0f, float(p[2]) / 255.0f, 0.f);
+  } else {
+    const float* p = (const float*)io.pixels + o;
+    c = make_float4(p[0], p[1], p[2], 0.f);
+  }
+  dst[i] = c;
+}
+
+__device__ __forceinline__ float atrous_h(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
+
+// One iteration of the edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) with
+// SVGF's normal and plane-distance weights: 5x5 taps `step` pixels apart, the
+// B3-spline kernel h = (1/16, 1/4, 3/8, 1/4, 1/16) per axis, times
+//   w_n = max(0, n_p . n_q) ^ sigmaNormal
+//   w_x = exp(-|n_p . (x_q - x_p)| / (sigmaPosition t_p))
+//   w_c = exp(-|c_p - c_q|^2 / sigmaColor_i^2)                  (rcpSigmaColor2 = 0: off)
+// Taps outside the image or on a miss are skipped; the centre tap weighs h(0)^2 exactly. The
+// mean is taken as c_p + sum w (c_q - c_p) / sum w, so a constant frame stays what it is.
+// A miss pixel is not written. The last iteration (out != null) stores into the framebuffer:
+// floats as they are, bytes as k_resolve_pixels quantizes them; alpha and row padding are
+// not touched.
+__global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const float4* __restrict__ pos4,
+                                                      const float4* __restrict__ nrm4, const float4* __restrict__ src,
+                                                      float4* __restrict__ dst, FrameIO out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)ap.width * ap.height) return;
+  const float INF = __int_as_float(0x7f800000);
+  const float4 pp = pos4[i];
+  if (!(pp.w < INF)) return;
+  const int y = (int)(i / ap.width), x = (int)(i - (long long)y * ap.width);
+  const float4 n4 = nrm4[i], c4 = src[i];
+  const V3 xp = v3(pp.x, pp.y, pp.z), np = v3(n4.x, n4.y, n4.z), cp = v3(c4.x, c4.y, c4.z);
+  const float rcpPlane = 1.0f / (ap.sigmaPosition * pp.w);
+  V3 sum = v3s(0.f);
+  float wsum = atrous_h(0) * atrous_h(0);
+  for (int dy = -2; dy <= 2; ++dy) {
+    const long long qy = (long long)y + (long long)dy * ap.step;
+    if (qy < 0 || qy >= ap.height) continue;
+    for (int dx = -2; dx <= 2; ++dx) {
+      const long long qx = (long long)x + (long long)dx * ap.step;
+      if (qx < 0 || qx >= ap.width || (dx == 0 && dy == 0)) continue;
+      const size_t j = (size_t)qy * ap.width + (size_t)qx;
+      const float4 pq = pos4[j];
+      if (!(pq.w < INF)) continue;
+      const float4 nq = nrm4[j], cq4 = src[j];
+      const V3 d = v3(cq4.x, cq4.y, cq4.z) - cp;
+      float w = atrous_h(dx) * atrous_h(dy);
+      w = w * yrt_powf(fmaxf(0.f, dot(np, v3(nq.x, nq.y, nq.z))), ap.sigmaNormal);
+      w = w * yrt_expf(-fabsf(dot(np, v3(pq.x, pq.y, pq.z) - xp)) * rcpPlane);
+      if (ap.rcpSigmaColor2 > 0.f) w = w * yrt_expf(-dot(d, d) * ap.rcpSigmaColor2);
+      sum = sum + w * d;
+      wsum = wsum + w;
+    }
+  }
+  const V3 c = cp + sum * (1.0f / wsum);
+  if (!out.pixels) {
+    dst[i] = make_float4(c.x, c.y, c.z, 0.f);
+    return;
+  }
+  const size_t o = fb_channel(out, x, y);
+  if (out.bytes) {
+    uint8_t* p = (uint8_t*)out.pixels + o;
+    p[0] = (uint8_t)clampf(c.x * 255.0f, 0.0f, 255.0f);
+    p[1] = (uint8_t)clampf(c.y * 255.0f, 0.0f, 255.0f);
+    p[2] = (uint8_t)clampf(c.z * 255.0f, 0.0f, 255.0f);
+  } else {
+    float* p = (float*)out.pixels + o;
+    p[0] = c.x;
+    p[1] = c.y;
+    p[2] = c.z;
+  }
 }
 
 // ---------------------------------------------------------------- arithmetic checks

@@ -367,7 +367,7 @@ __device__ int g_dbgPixel[3] = {-1, -1, 0};  // pixel id (y * width + x), frame,
 __device__ float4* g_dbgOut = nullptr;
 
 // AccuBuffer::update (api/framebuffer.h:289-304) + DefaultToneMapper::eval
-// (tonemappers/defaulttonemapper.h:23-36) + FrameBufferRGB8::set (api/framebuffer.h:220-226)
+// (tonemappers/defaulttonemapper.h:23-49) + FrameBufferRGB8::set (api/framebuffer.h:220-226)
 __global__ __launch_bounds__(YRT_BLOCK) void k_resolve_pixels(FrameView fv, PathBuffers pb, BatchInfo bi,
                                                             float* __restrict__ fbFloat, uint8_t* __restrict__ fbRGB8,
                                                             int rgb8Stride, float4* __restrict__ accu, int accumulate) {
@@ -393,6 +393,13 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_resolve_pixels(FrameView fv, Path
     accu[pix] = a;
     V3 L0 = accumulate ? v3(a.x, a.y, a.z) * rcpf_(a.w) : L * rcpf_((float)rp.spp);
     if (rp.gamma != 1.0f) L0 = v3(yrt_powf(L0.x, rp.rcpGamma), yrt_powf(L0.y, rp.rcpGamma), yrt_powf(L0.z, rp.rcpGamma));
+    if (rp.vignetting) {
+      // DefaultToneMapper::eval's vignette (tonemappers/defaulttonemapper.h:44-49), after the gamma
+      const float rw = rcpf_(0.5f * float(rp.width));
+      const float vx = (float(x) - 0.5f * float(rp.width)) * rw, vy = (float(y) - 0.5f * float(rp.height)) * rw;
+      const float d = sqrtf(vx * vx + vy * vy);
+      L0 = L0 * yrt_powf(yrt_cosf(d * 0.5f), 3.0f);
+    }
     if (fbFloat) {
       float* o = fbFloat + pix * 3;
       o[0] = L0.x;

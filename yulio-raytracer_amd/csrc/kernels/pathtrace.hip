@@ -232,6 +232,28 @@ void launch_pick(const SceneView& sv, const GpuCamera* cam, float x, float y, fl
   hipLaunchKernelGGL(k_pick, dim3(1), dim3(YRT_TRACE_BLOCK), 0, s, sv, cam, x, y, out);
 }
 
+void launch_guides(const SceneView& sv, const GpuCamera* cam, int width, int height, float4* pos4, float4* nrm4,
+                   hipStream_t s) {
+  const long long n = (long long)width * height;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_guides, dim3((unsigned)((n + YRT_TRACE_BLOCK - 1) / YRT_TRACE_BLOCK)), dim3(YRT_TRACE_BLOCK), 0,
+                     s, sv, cam, width, height, pos4, nrm4);
+}
+
+void launch_atrous_load(const FrameIO& io, float4* dst, hipStream_t s) {
+  const long long n = (long long)io.width * io.height;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_atrous_load, dim3((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK)), dim3(YRT_BLOCK), 0, s, io, dst);
+}
+
+void launch_atrous(const AtrousParams& ap, const float4* pos4, const float4* nrm4, const float4* src, float4* dst,
+                   const FrameIO& out, hipStream_t s) {
+  const long long n = (long long)ap.width * ap.height;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_atrous, dim3((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK)), dim3(YRT_BLOCK), 0, s, ap, pos4,
+                     nrm4, src, dst, out);
+}
+
 void launch_debug_render(const SceneView& sv, const FrameView& fv, int maxDepth, int spp, int numTiles, float* fbFloat,
                          uint8_t* fbRGB8, int rgb8Stride, hipStream_t s) {
   hipLaunchKernelGGL(k_debug, dim3((numTiles + 63) / 64), dim3(64), 0, s, sv, fv, maxDepth, spp, fbFloat, fbRGB8,

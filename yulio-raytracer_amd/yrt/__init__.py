@@ -257,6 +257,50 @@ class Device:
     def rtSwapBuffers(self, frameBuffer):
         self._rc(N.dev.yrtSwapBuffers(self.h, frameBuffer), "rtSwapBuffers")
 
+    # -- denoise (yrt_device.h: first-hit guide buffers + edge-avoiding a-trous filter)
+    def render_guides(self, camera, scene, width, height):
+        """(pos4, nrm4), float32 (height, width, 4) each: the first hit of the camera ray through
+        every pixel centre as (point, t) and (viewer-facing shading normal, 1); a miss is
+        (0, 0, 0, inf) and 0."""
+        pos = np.zeros((height, width, 4), np.float32)
+        nrm = np.zeros((height, width, 4), np.float32)
+        self._rc(N.dev.yrtRenderGuides(self.h, camera, scene, int(width), int(height), pos.ctypes.data,
+                                       nrm.ctypes.data), "render_guides")
+        return pos, nrm
+
+    @staticmethod
+    def denoise_defaults() -> dict:
+        """The library's default YRTDenoiseParams."""
+        p = N.DenoiseParams(size=C.sizeof(N.DenoiseParams))
+        if N.dev.yrtDenoiseDefaults(C.byref(p)) != 0:
+            raise RuntimeError("yrtDenoiseDefaults failed")
+        return {"iterations": p.iterations, "sigma_color": p.sigmaColor, "sigma_normal": p.sigmaNormal,
+                "sigma_position": p.sigmaPosition}
+
+    def denoise(self, camera, scene, frameBuffer, iterations=None, sigma_color=None, sigma_normal=None,
+                sigma_position=None):
+        """Filters frameBuffer's current frame in place, guided by the first hits seen through
+        `camera` (yrtDenoiseFrameBuffer). None: the library's default (5 iterations, sigma_color 1,
+        sigma_normal 64, sigma_position 0.02); sigma_color <= 0 turns the colour weight off."""
+        p = N.DenoiseParams(size=C.sizeof(N.DenoiseParams))
+        if N.dev.yrtDenoiseDefaults(C.byref(p)) != 0:
+            raise RuntimeError("yrtDenoiseDefaults failed")
+        if iterations is not None:
+            p.iterations = int(iterations)
+        if sigma_color is not None:
+            p.sigmaColor = float(sigma_color)
+        if sigma_normal is not None:
+            p.sigmaNormal = float(sigma_normal)
+        if sigma_position is not None:
+            p.sigmaPosition = float(sigma_position)
+        self._rc(N.dev.yrtDenoiseFrameBuffer(self.h, camera, scene, frameBuffer, C.byref(p)), "denoise")
+
+    def denoise_times(self):
+        """(ms of the last guide pass, ms of the last filter) by HIP events; set_kernel_timing first."""
+        a, b = C.c_float(), C.c_float()
+        self._rc(N.dev.yrtGetDenoiseTimes(self.h, C.byref(a), C.byref(b)), "denoise_times")
+        return a.value, b.value
+
     def rtSetStatusCallback(self, renderer, fn):
         cb = N.STATUS_CB(lambda s, p, u: fn(s, p))
         self._keep.append(cb)

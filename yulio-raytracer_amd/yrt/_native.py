@@ -75,6 +75,12 @@ class StatusRT(C.Structure):
     _fields_ = [("state", i32), ("progress", f32), ("lastError", i32)]
 
 
+class DenoiseParams(C.Structure):
+    """include/yrt_device.h YRTDenoiseParams; size = the bytes the caller's struct holds."""
+    _fields_ = [("size", C.c_uint32), ("iterations", i32), ("sigmaColor", f32), ("sigmaNormal", f32),
+                ("sigmaPosition", f32)]
+
+
 def _sig(lib, name, res, *args):
     fn = getattr(lib, name)
     fn.restype = res
@@ -177,6 +183,13 @@ except AttributeError:
     pass
 try:  # round 6; absent from older tuning builds selected with YRT_LIB_DIR
     _sig(dev, "yrtDebugTileScatter", i32, i32, i32)
+except AttributeError:
+    pass
+try:  # the denoise stage; absent from older builds selected with YRT_LIB_DIR
+    _sig(dev, "yrtRenderGuides", i32, vp, vp, vp, i32, i32, vp, vp)
+    _sig(dev, "yrtDenoiseDefaults", i32, C.POINTER(DenoiseParams))
+    _sig(dev, "yrtDenoiseFrameBuffer", i32, vp, vp, vp, vp, C.POINTER(DenoiseParams))
+    _sig(dev, "yrtGetDenoiseTimes", i32, vp, PF, PF)
 except AttributeError:
     pass
 _sig(dev, "yrtDebugDecodeImage", i32, cstr, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, sz)
