@@ -138,16 +138,35 @@ YRT_API int yrtPick(YRTDevice dev, YRTHandle camera, float x, float y, YRTHandle
  * i = y * width + x; a miss gives (0, 0, 0, +inf) and (0, 0, 0, 0). width * height * 4 floats each. */
 YRT_API int yrtRenderGuides(YRTDevice dev, YRTHandle camera, YRTHandle scene, int width, int height,
                             float* pos4Host, float* nrm4Host);
+/* yrtRenderAlbedo: the first-hit albedo of the same rays, albedo4Host[4 i] = (albedo, 1), a miss
+ * (0, 0, 0, 0); width * height * 4 floats. The albedo is the per-channel sum of the reflectances
+ * of the diffuse-reflection components the hit's material creates there, textures included
+ * (Matte, MatteTextured and Uber x texture x alpha, Obj d Kd map_Kd, the Plastic and MetallicPaint
+ * pigment, both Velvet lobes), evaluated in the medium a camera ray starts in; it is (1, 1, 1)
+ * where there is no such component (mirror, metal, dielectrics), where the sum is 0 and on a light
+ * primitive. The guide normals are postIntersect's: an Obj bump map does not reach them. */
+YRT_API int yrtRenderAlbedo(YRTDevice dev, YRTHandle camera, YRTHandle scene, int width, int height,
+                            float* albedo4Host);
 /* size = sizeof(YRTDenoiseParams) of the caller's build, checked: a shorter struct is read up to
  * its size and the remaining fields take their defaults; below sizeof(size) is an error.
  * iterations: filter passes, step 2^i (0: the call writes nothing). sigmaColor: colour weight
  * exp(-|dc|^2 / (sigmaColor 2^-i)^2), <= 0 turns it off. sigmaNormal: exponent of
  * max(0, n_p . n_q). sigmaPosition: plane-distance weight exp(-|n_p . (x_q - x_p)| /
- * (sigmaPosition t_p)). Defaults: 5, 1, 64, 0.02 (yrtDenoiseDefaults). */
+ * (sigmaPosition t_p)). Defaults: 5, 1, 64, 0.02 (yrtDenoiseDefaults).
+ * demodulate != 0: the texture-preserving filter. The frame is divided by the modulation
+ * m = max(albedo, albedoFloor) ^ albedoPower per channel (yrtRenderAlbedo's albedo of the pixel),
+ * the iterations run on the quotient, colour weight included, and the last one stores the result
+ * times m. albedoPower: 1 / gamma of the tone mapper the frame went through, since
+ * (a L)^(1/gamma) = a^(1/gamma) L^(1/gamma); the vignette is a per-pixel factor and cancels.
+ * albedoFloor keeps the division away from 0. Both must be finite and > 0 and are checked only when
+ * demodulate is set; demodulate = 0 (the default, and a struct that ends before it) is the plain
+ * filter, bit for bit. Defaults: 0, 1, 1/255. */
 typedef struct YRTDenoiseParams {
   uint32_t size;
   int iterations;
   float sigmaColor, sigmaNormal, sigmaPosition;
+  int demodulate;
+  float albedoPower, albedoFloor;
 } YRTDenoiseParams;
 /* Fills the fields that fit into p->size (set by the caller) with the library's defaults. */
 YRT_API int yrtDenoiseDefaults(YRTDenoiseParams* p);
@@ -164,7 +183,8 @@ YRT_API int yrtDenoiseDefaults(YRTDenoiseParams* p);
 YRT_API int yrtDenoiseFrameBuffer(YRTDevice dev, YRTHandle camera, YRTHandle scene, YRTHandle framebuffer,
                                   const YRTDenoiseParams* p);
 /* With yrtSetKernelTiming on: HIP-event times, in ms, of the kernels of the last guide pass
- * (yrtRenderGuides, or the one inside yrtDenoiseFrameBuffer) and of the last filter (its load and
+ * (yrtRenderGuides, yrtRenderAlbedo, or the one inside yrtDenoiseFrameBuffer, which renders the
+ * albedo in the same kernel when demodulate is set) and of the last filter (its load and
  * iterations, without the guide pass and any host copy). Either pointer may be NULL. */
 YRT_API int yrtGetDenoiseTimes(YRTDevice dev, float* msGuides, float* msFilter);
 /* Renderer status callback (device.h:335-347): state 0 Inactive, 1 Rendering, 2 Done. */

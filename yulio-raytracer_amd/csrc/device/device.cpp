@@ -94,7 +94,7 @@ struct GpuCtx {
   DevBuf dRp, dCam, dPixelSets, dAccu, dCount, dSpill, dSlab, dDirect;
   // denoise (yrtRenderGuides / yrtDenoiseFrameBuffer): the guide frames, the filter's two
   // ping-pong float4 frames and the upload of a frame that lives in host pixels
-  DevBuf dGuidePos, dGuideNrm, dFilter[2], dFilterFb;
+  DevBuf dGuidePos, dGuideNrm, dGuideAlbedo, dFilter[2], dFilterMod, dFilterFb;
   // The frames a job renders into (float RGB and RGB8 rows, frame-major). On the primary
   // device a job's framebuffers keep a reference to their block until rtMapFrameBuffer reads
   // them back, so the next job renders into the spare (or a fresh) block meanwhile.
@@ -358,8 +358,8 @@ class Device {
   void intersect(SceneObj& S, const float* org4, const float* dir4, uint32_t n, float* hit4, int32_t* occ,
                  hipStream_t st);
   // the first-hit guide frames of a W x H view of C in ctx[0]'s dGuidePos / dGuideNrm (enqueued
-  // on the primary stream)
-  void guides(CameraObj& C, SceneObj& S, int W, int H, const char* what);
+  // on the primary stream); albedo: the same pass also fills dGuideAlbedo (k_guides<true>)
+  void guides(CameraObj& C, SceneObj& S, int W, int H, const char* what, bool albedo = false);
   // yrtSetKernelTiming: HIP-event times of the last guide pass and the last filter (its load and
   // iterations), yrtGetDenoiseTimes; the events are read once the stream has been synchronized
   struct EvPair {
@@ -579,7 +579,7 @@ void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& 
 }
 
 // ---------------------------------------------------------------- denoise
-void Device::guides(CameraObj& C, SceneObj& S, int W, int H, const char* what) {
+void Device::guides(CameraObj& C, SceneObj& S, int W, int H, const char* what, bool albedo) {
   if (!S.gpu) throw std::runtime_error(std::string(what) + ": scene not committed");
   if (S.gpu->device != hipDevice) throw std::runtime_error(std::string(what) + ": scene committed on another HIP device");
   // one thread per pixel in 64-lane blocks: the grid stays far inside 2^31 blocks
@@ -590,9 +590,11 @@ void Device::guides(CameraObj& C, SceneObj& S, int W, int H, const char* what) {
   g.dCam.alloc(sizeof(GpuCamera));
   g.dGuidePos.alloc(bytes);
   g.dGuideNrm.alloc(bytes);
+  if (albedo) g.dGuideAlbedo.alloc(bytes);
   HIP_CHECK(hipMemcpyAsync(g.dCam.p, &C.cam, sizeof(GpuCamera), hipMemcpyHostToDevice, stream));
   evGuides.start(kernelTiming, stream);
-  launch_guides(S.gpu->view, g.dCam.as<GpuCamera>(), W, H, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(), stream);
+  launch_guides(S.gpu->view, g.dCam.as<GpuCamera>(), W, H, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(),
+                albedo ? g.dGuideAlbedo.as<float4>() : nullptr, stream);
   evGuides.stop(stream);
   HIP_CHECK(hipGetLastError());
 }
@@ -604,12 +606,16 @@ void Device::guides(CameraObj& C, SceneObj& S, int W, int H, const char* what) {
 // formats exist on the host only (fb_read_back converts the block's RGB floats), so such a frame
 // is read back first and, like any frame already mapped or rendered into user pointers,
 // uploaded from the host pixels, filtered and copied back into them.
+// demodulate: the guide pass also renders the first-hit albedo, the load divides the frame by the
+// modulation max(albedo, albedoFloor) ^ albedoPower and the last iteration multiplies it back
+// (k_atrous<true>); clear, the kernels are the <false> instantiations: no albedo, today's arithmetic.
 void Device::denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDenoiseParams& p) {
   if (!S.gpu) throw std::runtime_error("yrtDenoiseFrameBuffer: scene not committed");
   if (p.iterations == 0) return;
   const int W = F.width, H = F.height, id = F.cur;
   if (W < 1 || H < 1) return;
-  guides(C, S, W, H, "yrtDenoiseFrameBuffer");
+  const bool demod = p.demodulate != 0;
+  guides(C, S, W, H, "yrtDenoiseFrameBuffer", demod);
   GpuCtx& g = *ctx[0];
   const bool bytes8 = F.format == FB_RGB8 || F.format == FB_RGBA8;
   const bool rgba = F.format == FB_RGBA8 || F.format == FB_RGBA_FLOAT32;
@@ -634,8 +640,16 @@ void Device::denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDeno
   const size_t frameBytes = (size_t)W * H * sizeof(float4);
   g.dFilter[0].alloc(frameBytes);
   if (p.iterations > 1) g.dFilter[1].alloc(frameBytes);
+  Demodulation dm;
+  if (demod) {
+    g.dFilterMod.alloc(frameBytes);
+    dm.albedo4 = g.dGuideAlbedo.as<float4>();
+    dm.mod4 = g.dFilterMod.as<float4>();
+    dm.albedoFloor = p.albedoFloor;
+    dm.albedoPower = p.albedoPower;
+  }
   evFilter.start(kernelTiming, stream);
-  launch_atrous_load(io, g.dFilter[0].as<float4>(), stream);
+  launch_atrous_load(io, g.dFilter[0].as<float4>(), dm, stream);
   AtrousParams ap;
   memset(&ap, 0, sizeof(ap));
   ap.width = W;
@@ -650,7 +664,7 @@ void Device::denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDeno
     const float sc = p.sigmaColor > 0.f ? p.sigmaColor / (float)(1 << i) : 0.f;
     ap.rcpSigmaColor2 = sc > 0.f ? 1.0f / (sc * sc) : 0.f;
     launch_atrous(ap, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(), g.dFilter[i & 1].as<float4>(),
-                  last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(), last ? io : none, stream);
+                  last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(), last ? io : none, dm.mod4, stream);
   }
   evFilter.stop(stream);
   HIP_CHECK(hipGetLastError());
@@ -1976,7 +1990,8 @@ int yrtPick(YRTDevice dev, YRTHandle camera, float x, float y, YRTHandle scene, 
 
 // The library's YRTDenoiseParams: the defaults overlaid by the fields the caller's struct holds.
 // sigmaColor 1: the lowest mean squared error against a 1024-spp frame, summed over C1 and C2,
-// among 0.25, 0.5, 1, 2 and off.
+// among 0.25, 0.5, 1, 2 and off. albedoFloor 1/255: the 8-bit texel quantum, the
+// smallest non-zero albedo an 8-bit texture can hold (§9).
 static YRTDenoiseParams denoise_params(const YRTDenoiseParams* p) {
   YRTDenoiseParams d;
   d.size = (uint32_t)sizeof(YRTDenoiseParams);
@@ -1984,6 +1999,9 @@ static YRTDenoiseParams denoise_params(const YRTDenoiseParams* p) {
   d.sigmaColor = 1.0f;
   d.sigmaNormal = 64.f;
   d.sigmaPosition = 0.02f;
+  d.demodulate = 0;
+  d.albedoPower = 1.0f;
+  d.albedoFloor = 1.0f / 255.0f;
   if (!p) return d;
   if (p->size < sizeof(uint32_t)) throw std::runtime_error("YRTDenoiseParams: size is smaller than the size field");
   const size_t n = p->size;
@@ -1993,10 +2011,18 @@ static YRTDenoiseParams denoise_params(const YRTDenoiseParams* p) {
   YRT_DN_FIELD(sigmaColor);
   YRT_DN_FIELD(sigmaNormal);
   YRT_DN_FIELD(sigmaPosition);
+  YRT_DN_FIELD(demodulate);
+  YRT_DN_FIELD(albedoPower);
+  YRT_DN_FIELD(albedoFloor);
 #undef YRT_DN_FIELD
   if (d.iterations < 0 || d.iterations > 16) throw std::runtime_error("YRTDenoiseParams: iterations outside 0..16");
   if (!(d.sigmaNormal >= 0.f) || !(d.sigmaPosition > 0.f) || d.sigmaColor != d.sigmaColor)
     throw std::runtime_error("YRTDenoiseParams: sigmaNormal >= 0 and sigmaPosition > 0 are required");
+  const auto positive = [](float v) { return v > 0.f && v <= 3.40282347e38f; };
+  if (d.demodulate != 0 && !positive(d.albedoPower))
+    throw std::runtime_error("YRTDenoiseParams: demodulate needs a finite albedoPower > 0");
+  if (d.demodulate != 0 && !positive(d.albedoFloor))
+    throw std::runtime_error("YRTDenoiseParams: demodulate needs a finite albedoFloor > 0");
   return d;
 }
 
@@ -2022,6 +2048,24 @@ int yrtRenderGuides(YRTDevice dev, YRTHandle camera, YRTHandle scene, int width,
   const size_t bytes = (size_t)width * height * sizeof(float4);
   HIP_CHECK(hipMemcpyAsync(pos4Host, g.dGuidePos.p, bytes, hipMemcpyDeviceToHost, D.stream));
   HIP_CHECK(hipMemcpyAsync(nrm4Host, g.dGuideNrm.p, bytes, hipMemcpyDeviceToHost, D.stream));
+  HIP_CHECK(hipStreamSynchronize(D.stream));
+  D.evGuides.read(D.msGuides);
+  return 0;
+  DEV_END(-1)
+}
+
+int yrtRenderAlbedo(YRTDevice dev, YRTHandle camera, YRTHandle scene, int width, int height, float* albedo4Host) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  if (!D.gpu) throw std::runtime_error("yrtRenderAlbedo: host-only device (created with parms \"host\")");
+  auto C = D.get<CameraObj>(camera, "camera");
+  auto S = D.get<SceneObj>(scene, "scene");
+  if (!C || !S || !albedo4Host) throw std::runtime_error("yrtRenderAlbedo: null handle or pointer");
+  if (width < 1 || height < 1) throw std::runtime_error("yrtRenderAlbedo: empty frame");
+  D.guides(*C, *S, width, height, "yrtRenderAlbedo", true);
+  GpuCtx& g = *D.ctx[0];
+  const size_t bytes = (size_t)width * height * sizeof(float4);
+  HIP_CHECK(hipMemcpyAsync(albedo4Host, g.dGuideAlbedo.p, bytes, hipMemcpyDeviceToHost, D.stream));
   HIP_CHECK(hipStreamSynchronize(D.stream));
   D.evGuides.read(D.msGuides);
   return 0;

@@ -94,11 +94,12 @@ struct Stream {
   std::string peek() const { return i < t.size() ? t[i] : ""; }
   std::string get() { return i < t.size() ? t[i++] : ""; }
   void drop() { i++; }
-  float getFloat() {
+  double getDouble() {
     const std::string s = get();
     if (s.empty()) throw std::runtime_error("number expected");
-    return (float)atof(s.c_str());
+    return atof(s.c_str());
   }
+  float getFloat() { return (float)getDouble(); }
   int getInt() {
     const std::string s = get();
     if (s.empty()) throw std::runtime_error("integer expected");
@@ -301,7 +302,9 @@ void RtState::parseCommandLine(const std::vector<std::string>& tokens, const std
       }
       check(dev, yrtCommit(dev, renderer), "rtCommit(renderer)");
     } else if (tag == "-gamma") {
-      gamma = cin.getFloat();
+      const double g = cin.getDouble();
+      gamma = (float)g;
+      rcpGamma = 1.0 / g;
       check(dev, yrtSetFloat1(dev, tonemapper, "gamma", gamma), "rtSetFloat1");
       check(dev, yrtCommit(dev, tonemapper), "rtCommit(tonemapper)");
     } else if (tag == "-vignetting") {
@@ -311,6 +314,10 @@ void RtState::parseCommandLine(const std::vector<std::string>& tokens, const std
     } else if (tag == "-denoise") {
       denoise = cin.getInt();
       if (denoise < 0) throw std::runtime_error("-denoise: the iteration count must not be negative");
+    } else if (tag == "-denoise-albedo") {
+      const int v = cin.getInt();
+      if (v != 0 && v != 1) throw std::runtime_error("-denoise-albedo: 0 or 1 expected");
+      denoiseAlbedo = v == 1;
     } else if (tag == "-depth") {
       depth = cin.getInt();
       check(dev, yrtSetInt1(dev, renderer, "maxDepth", depth), "rtSetInt1");
@@ -594,6 +601,13 @@ void RtState::denoiseFrame(YRTHandle cam, YRTHandle sc, YRTHandle fb) {
   if (denoise <= 0) return;
   YRTDenoiseParams p;
   p.size = (uint32_t)(offsetof(YRTDenoiseParams, iterations) + sizeof(p.iterations));  // the weights: defaults
+  if (denoiseAlbedo) {
+    // the frame is tone mapped: (a L)^(1/gamma) = a^(1/gamma) L^(1/gamma)
+    p.size = (uint32_t)sizeof(p);
+    if (yrtDenoiseDefaults(&p) != 0) throw std::runtime_error("yrtDenoiseDefaults failed");
+    p.demodulate = 1;
+    p.albedoPower = (float)rcpGamma;
+  }
   p.iterations = denoise;
   check(dev, yrtDenoiseFrameBuffer(dev, cam, sc, fb, &p), "yrtDenoiseFrameBuffer");
 }

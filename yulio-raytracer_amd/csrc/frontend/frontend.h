@@ -102,8 +102,10 @@ struct RtState {
   std::string sceneType = "default", accel = "default", builder = "default", traverser = "default";
   int depth = -1, spp = 1, numBuffers = 1;
   float gamma = 1.0f;
+  double rcpGamma = 1.0;  // 1 / the -gamma argument as written: the demodulated denoiser's albedoPower
   bool vignetting = false;
   int denoise = 0;  // -denoise <iterations>: a-trous passes over every rendered frame (0: off)
+  bool denoiseAlbedo = false;  // -denoise-albedo <0|1>: demodulate by the first-hit albedo (with -denoise)
   int width = 512, height = 512;
   std::string format = "RGB8";
   std::string outFileName;
@@ -126,7 +128,8 @@ struct RtState {
   YRTHandle createCamera(int face);
   YRTHandle createScene();
   // -denoise: filters the frame just rendered into fb through cam (yrtDenoiseFrameBuffer with the
-  // library's default weights), before it is read, watermarked or assembled into a strip
+  // library's default weights; -denoise-albedo 1: demodulated, albedoPower = 1 / gamma), before it
+  // is read, watermarked or assembled into a strip
   void denoiseFrame(YRTHandle cam, YRTHandle sc, YRTHandle fb);
   void outputMode(const std::string& file, std::vector<uint8_t>* outImage = nullptr);
   // FPR branch of outputMode (renderer.cpp:519-737): per camera view, update faceCamera

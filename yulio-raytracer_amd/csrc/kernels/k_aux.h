@@ -181,8 +181,18 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) void k_pick(SceneView sv, const Gp
 // caller computes for rtPick), time 0, and stores pos4 = (org + t dir, t) and nrm4 = (Ns, 1)
 // with postIntersect's shading normal turned towards the viewer; a miss stores (0, 0, 0, inf)
 // and 0.
+// ALBEDO (yrtRenderAlbedo, the demodulated filter): the same ray and hit also store
+// albedo4 = (first-hit albedo, 1), a miss +0: Material::shade of the hit's material, evaluated
+// on a copy of the differential geometry (Obj's bump map turns dg.Ns; the normal guide keeps
+// postIntersect's) in the medium a camera ray starts in (vacuum, k_shade's depth 0), with
+// k_shade's every-material instantiation and its tex_get / tex_get_rec. The albedo is the sum
+// of R over the diffuse-reflection components; (1, 1, 1) where there is none, where the sum is
+// 0 and on a light primitive. Off the render loop: its component set may live
+// in scratch.
+template <bool ALBEDO>
 __global__ __launch_bounds__(YRT_TRACE_BLOCK) void k_guides(SceneView sv, const GpuCamera* camp, int width, int height,
-                                                            float4* __restrict__ pos4, float4* __restrict__ nrm4) {
+                                                            float4* __restrict__ pos4, float4* __restrict__ nrm4,
+                                                            float4* __restrict__ albedo4) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)width * height) return;
   const int y = (int)(i / width), x = (int)(i - (long long)y * width);
@@ -198,14 +208,34 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) void k_guides(SceneView sv, const 
   if (h.tri < 0) {
     pos4[i] = make_float4(0.f, 0.f, 0.f, __int_as_float(0x7f800000));
     nrm4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (ALBEDO) albedo4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
   DG dg;
-  post_intersect_g(sv, sv.geoms[sv.triGeom[h.tri]], org, dir, h.t, h.u, h.v, h.tri, dg, false);
+  const int g = sv.triGeom[h.tri];
+  post_intersect_g(sv, sv.geoms[g], org, dir, h.t, h.u, h.v, h.tri, dg, false);
   V3 n = dg.Ns;
   if (dot(n, dir) > 0.f) n = -n;
   pos4[i] = make_float4(dg.P.x, dg.P.y, dg.P.z, h.t);
   nrm4[i] = make_float4(n.x, n.y, n.z, 1.f);
+  if constexpr (ALBEDO) {
+    V3 a = v3s(0.f);
+    if (dg.light < 0 && dg.material >= 0) {
+      DG sdg = dg;  // shade_material may turn its Ns
+      if (dot(sdg.Ng, dir) > 0.f) {  // k_shade hands Material::shade the viewer-facing side
+        sdg.Ng = -sdg.Ng;
+        sdg.Ns = -sdg.Ns;
+      }
+      BRDFSet bs;
+      const GpuGeomRec& gr = sv.geomRecs[g];
+      shade_material<YRT_ALL_MATS>(sv, gr.m, gr.t0, sdg.material, 0, sdg, bs);
+#pragma unroll
+      for (int k = 0; k < YRT_MAX_COMPS; ++k)
+        if (k < bs.n && comp_type(bs.c[k].kind) == BT_DIFFUSE_REFLECTION) a = a + bs.c[k].R;
+    }
+    if (a == v3s(0.f)) a = v3s(1.f);
+    albedo4[i] = make_float4(a.x, a.y, a.z, 1.f);
+  }
 }
 
 // A framebuffer as the filter reads and writes it: float or 8-bit channels, 3 or 4 per pixel,
@@ -214,8 +244,14 @@ __device__ __forceinline__ size_t fb_channel(const FrameIO& io, int x, int y) {
   return (size_t)y * io.rowStride + (size_t)x * io.pixStride;
 }
 
-// c_0 of the filter: the framebuffer's pixels as float4 (8-bit channels as byte / 255)
-__global__ __launch_bounds__(YRT_BLOCK) void k_atrous_load(FrameIO io, float4* __restrict__ dst) {
+// c_0 of the filter: the framebuffer's pixels as float4 (8-bit channels as byte / 255).
+// DEMOD (YRTDenoiseParams::demodulate): a hit pixel's modulation m = max(albedo, floor) ^ power
+// per channel goes to mod4 and the filter's input is d_0 = c_0 / m (IEEE divisions); a miss
+// pixel, which the filter neither reads nor writes, keeps c_0 and gets m = 1.
+template <bool DEMOD>
+__global__ __launch_bounds__(YRT_BLOCK) void k_atrous_load(FrameIO io, float4* __restrict__ dst,
+                                                           const float4* __restrict__ albedo4, float albedoFloor,
+                                                           float albedoPower, float4* __restrict__ mod4) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)io.width * io.height) return;
   const int y = (int)(i / io.width), x = (int)(i - (long long)y * io.width);
@@ -227,6 +263,17 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_atrous_load(FrameIO io, float4* _
   } else {
     const float* p = (const float*)io.pixels + o;
     c = make_float4(p[0], p[1], p[2], 0.f);
+  }
+  if constexpr (DEMOD) {
+    const float4 a = albedo4[i];
+    float4 m = make_float4(1.f, 1.f, 1.f, 0.f);
+    if (a.w != 0.f) {
+      m.x = yrt_powf(fmaxf(a.x, albedoFloor), albedoPower);
+      m.y = yrt_powf(fmaxf(a.y, albedoFloor), albedoPower);
+      m.z = yrt_powf(fmaxf(a.z, albedoFloor), albedoPower);
+      c = make_float4(c.x / m.x, c.y / m.y, c.z / m.z, 0.f);
+    }
+    mod4[i] = m;
   }
   dst[i] = c;
 }
@@ -243,10 +290,13 @@ __device__ __forceinline__ float atrous_h(int d) { return d == 0 ? 0.375f : (d =
 // mean is taken as c_p + sum w (c_q - c_p) / sum w, so a constant frame stays what it is.
 // A miss pixel is not written. The last iteration (out != null) stores into the framebuffer:
 // floats as they are, bytes as k_resolve_pixels quantizes them; alpha and row padding are
-// not touched.
+// not touched. DEMOD: the frames hold the demodulated signal d (k_atrous_load), every weight
+// acts on d, and the last iteration stores d_n m with the modulation of mod4.
+template <bool DEMOD>
 __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const float4* __restrict__ pos4,
                                                       const float4* __restrict__ nrm4, const float4* __restrict__ src,
-                                                      float4* __restrict__ dst, FrameIO out) {
+                                                      float4* __restrict__ dst, FrameIO out,
+                                                      const float4* __restrict__ mod4) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)ap.width * ap.height) return;
   const float INF = __int_as_float(0x7f800000);
@@ -277,10 +327,14 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const flo
       wsum = wsum + w;
     }
   }
-  const V3 c = cp + sum * (1.0f / wsum);
+  V3 c = cp + sum * (1.0f / wsum);
   if (!out.pixels) {
     dst[i] = make_float4(c.x, c.y, c.z, 0.f);
     return;
+  }
+  if constexpr (DEMOD) {
+    const float4 m = mod4[i];
+    c = c * v3(m.x, m.y, m.z);
   }
   const size_t o = fb_channel(out, x, y);
   if (out.bytes) {

@@ -233,25 +233,39 @@ void launch_pick(const SceneView& sv, const GpuCamera* cam, float x, float y, fl
 }
 
 void launch_guides(const SceneView& sv, const GpuCamera* cam, int width, int height, float4* pos4, float4* nrm4,
-                   hipStream_t s) {
+                   float4* albedo4, hipStream_t s) {
   const long long n = (long long)width * height;
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_guides, dim3((unsigned)((n + YRT_TRACE_BLOCK - 1) / YRT_TRACE_BLOCK)), dim3(YRT_TRACE_BLOCK), 0,
-                     s, sv, cam, width, height, pos4, nrm4);
+  const dim3 grid((unsigned)((n + YRT_TRACE_BLOCK - 1) / YRT_TRACE_BLOCK));
+  if (albedo4)
+    hipLaunchKernelGGL(k_guides<true>, grid, dim3(YRT_TRACE_BLOCK), 0, s, sv, cam, width, height, pos4, nrm4, albedo4);
+  else
+    hipLaunchKernelGGL(k_guides<false>, grid, dim3(YRT_TRACE_BLOCK), 0, s, sv, cam, width, height, pos4, nrm4,
+                       (float4*)nullptr);
 }
 
-void launch_atrous_load(const FrameIO& io, float4* dst, hipStream_t s) {
+void launch_atrous_load(const FrameIO& io, float4* dst, const Demodulation& dm, hipStream_t s) {
   const long long n = (long long)io.width * io.height;
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_atrous_load, dim3((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK)), dim3(YRT_BLOCK), 0, s, io, dst);
+  const dim3 grid((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK));
+  if (dm.mod4)
+    hipLaunchKernelGGL(k_atrous_load<true>, grid, dim3(YRT_BLOCK), 0, s, io, dst, dm.albedo4, dm.albedoFloor,
+                       dm.albedoPower, dm.mod4);
+  else
+    hipLaunchKernelGGL(k_atrous_load<false>, grid, dim3(YRT_BLOCK), 0, s, io, dst, (const float4*)nullptr, 0.f, 0.f,
+                       (float4*)nullptr);
 }
 
 void launch_atrous(const AtrousParams& ap, const float4* pos4, const float4* nrm4, const float4* src, float4* dst,
-                   const FrameIO& out, hipStream_t s) {
+                   const FrameIO& out, const float4* mod4, hipStream_t s) {
   const long long n = (long long)ap.width * ap.height;
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_atrous, dim3((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK)), dim3(YRT_BLOCK), 0, s, ap, pos4,
-                     nrm4, src, dst, out);
+  const dim3 grid((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK));
+  if (mod4)
+    hipLaunchKernelGGL(k_atrous<true>, grid, dim3(YRT_BLOCK), 0, s, ap, pos4, nrm4, src, dst, out, mod4);
+  else
+    hipLaunchKernelGGL(k_atrous<false>, grid, dim3(YRT_BLOCK), 0, s, ap, pos4, nrm4, src, dst, out,
+                       (const float4*)nullptr);
 }
 
 void launch_debug_render(const SceneView& sv, const FrameView& fv, int maxDepth, int spp, int numTiles, float* fbFloat,

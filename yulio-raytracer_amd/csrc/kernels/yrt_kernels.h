@@ -202,11 +202,12 @@ void launch_pack_tiles(const float* fbFloat, const uint8_t* fbRGB8, const SlabLa
 void launch_unpack_tiles(const void* slab, float* fbFloat, uint8_t* fbRGB8, const SlabLayout& L, int numTiles,
                          hipStream_t s);
 void launch_pick(const SceneView& sv, const GpuCamera* cam, float x, float y, float4* out, hipStream_t s);
-// Denoise (yrtRenderGuides / yrtDenoiseFrameBuffer, k_aux.h). launch_guides: the first-hit guide
-// frames of a width x height view of `cam`, one thread per pixel: pos4 = (hit point, t),
-// nrm4 = (viewer-facing shading normal, 1); misses (0, 0, 0, inf) and 0.
+// Denoise (yrtRenderGuides / yrtRenderAlbedo / yrtDenoiseFrameBuffer, k_aux.h). launch_guides:
+// the first-hit guide frames of a width x height view of `cam`, one thread per pixel:
+// pos4 = (hit point, t), nrm4 = (viewer-facing shading normal, 1); misses (0, 0, 0, inf) and 0.
+// albedo4 != null: the same pass also stores (first-hit albedo, 1), misses 0 (k_guides<true>).
 void launch_guides(const SceneView& sv, const GpuCamera* cam, int width, int height, float4* pos4, float4* nrm4,
-                   hipStream_t s);
+                   float4* albedo4, hipStream_t s);
 // A framebuffer's pixels in device memory: float (bytes = 0) or 8-bit (bytes = 1) channels,
 // pixStride (3 or 4) per pixel, rows rowStride channels apart; pixels = null: none
 struct FrameIO {
@@ -219,11 +220,19 @@ struct AtrousParams {
   float rcpSigmaColor2;  // 1 / sigmaColor_i^2 of this iteration; 0: no colour weight
   float sigmaNormal, sigmaPosition, pad2;
 };
-// c_0: the framebuffer's pixels as float4 (8-bit channels / 255)
-void launch_atrous_load(const FrameIO& io, float4* dst, hipStream_t s);
-// one filter iteration src -> dst (float4 frames), or src -> the framebuffer `out` (the last one)
+// The demodulated filter (YRTDenoiseParams::demodulate): albedo4 = launch_guides' albedo frame,
+// mod4 receives the modulation max(albedo, albedoFloor) ^ albedoPower; mod4 = null: off
+struct Demodulation {
+  const float4* albedo4 = nullptr;
+  float4* mod4 = nullptr;
+  float albedoFloor = 0.f, albedoPower = 0.f;
+};
+// c_0: the framebuffer's pixels as float4 (8-bit channels / 255); demodulated: c_0 / modulation
+void launch_atrous_load(const FrameIO& io, float4* dst, const Demodulation& dm, hipStream_t s);
+// one filter iteration src -> dst (float4 frames), or src -> the framebuffer `out` (the last one,
+// times the modulation mod4 when that is not null)
 void launch_atrous(const AtrousParams& ap, const float4* pos4, const float4* nrm4, const float4* src, float4* dst,
-                   const FrameIO& out, hipStream_t s);
+                   const FrameIO& out, const float4* mod4, hipStream_t s);
 // BVH refit after faceCamera updates: rewrite triangles [firstTri, firstTri+numTris) (global
 // ids) from the vertex buffer in every leaf slot that references them (leafSlots[leafStart[g]
 // .. leafStart[g+1])), then refit one tree level of nodes (call deepest level first)

@@ -268,20 +268,34 @@ class Device:
                                        nrm.ctypes.data), "render_guides")
         return pos, nrm
 
+    def render_albedo(self, camera, scene, width, height):
+        """albedo4, float32 (height, width, 4): (first-hit albedo, 1) of render_guides' rays, the
+        summed reflectance of the hit material's diffuse components, textures included; (1, 1, 1)
+        where it has none or on a light, 0 on a miss (yrtRenderAlbedo)."""
+        alb = np.zeros((height, width, 4), np.float32)
+        self._rc(N.dev.yrtRenderAlbedo(self.h, camera, scene, int(width), int(height), alb.ctypes.data),
+                 "render_albedo")
+        return alb
+
     @staticmethod
-    def denoise_defaults() -> dict:
-        """The library's default YRTDenoiseParams."""
+    def denoise_defaults(extended=False) -> dict:
+        """The library's default YRTDenoiseParams; extended: with the demodulation fields."""
         p = N.DenoiseParams(size=C.sizeof(N.DenoiseParams))
         if N.dev.yrtDenoiseDefaults(C.byref(p)) != 0:
             raise RuntimeError("yrtDenoiseDefaults failed")
-        return {"iterations": p.iterations, "sigma_color": p.sigmaColor, "sigma_normal": p.sigmaNormal,
-                "sigma_position": p.sigmaPosition}
+        d = {"iterations": p.iterations, "sigma_color": p.sigmaColor, "sigma_normal": p.sigmaNormal,
+             "sigma_position": p.sigmaPosition}
+        if extended:
+            d.update(demodulate=p.demodulate, albedo_power=p.albedoPower, albedo_floor=p.albedoFloor)
+        return d
 
     def denoise(self, camera, scene, frameBuffer, iterations=None, sigma_color=None, sigma_normal=None,
-                sigma_position=None):
+                sigma_position=None, demodulate=None, albedo_power=None, albedo_floor=None):
         """Filters frameBuffer's current frame in place, guided by the first hits seen through
         `camera` (yrtDenoiseFrameBuffer). None: the library's default (5 iterations, sigma_color 1,
-        sigma_normal 64, sigma_position 0.02); sigma_color <= 0 turns the colour weight off."""
+        sigma_normal 64, sigma_position 0.02); sigma_color <= 0 turns the colour weight off.
+        demodulate: filter frame / m and store the result x m, m = max(albedo, albedo_floor) ^
+        albedo_power; albedo_power is 1 / gamma of the frame's tone mapper (defaults 0, 1, 1/255)."""
         p = N.DenoiseParams(size=C.sizeof(N.DenoiseParams))
         if N.dev.yrtDenoiseDefaults(C.byref(p)) != 0:
             raise RuntimeError("yrtDenoiseDefaults failed")
@@ -293,6 +307,12 @@ class Device:
             p.sigmaNormal = float(sigma_normal)
         if sigma_position is not None:
             p.sigmaPosition = float(sigma_position)
+        if demodulate is not None:
+            p.demodulate = int(demodulate)
+        if albedo_power is not None:
+            p.albedoPower = float(albedo_power)
+        if albedo_floor is not None:
+            p.albedoFloor = float(albedo_floor)
         self._rc(N.dev.yrtDenoiseFrameBuffer(self.h, camera, scene, frameBuffer, C.byref(p)), "denoise")
 
     def denoise_times(self):

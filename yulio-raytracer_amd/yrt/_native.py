@@ -78,7 +78,7 @@ class StatusRT(C.Structure):
 class DenoiseParams(C.Structure):
     """include/yrt_device.h YRTDenoiseParams; size = the bytes the caller's struct holds."""
     _fields_ = [("size", C.c_uint32), ("iterations", i32), ("sigmaColor", f32), ("sigmaNormal", f32),
-                ("sigmaPosition", f32)]
+                ("sigmaPosition", f32), ("demodulate", i32), ("albedoPower", f32), ("albedoFloor", f32)]
 
 
 def _sig(lib, name, res, *args):
@@ -190,6 +190,7 @@ try:  # the denoise stage; absent from older builds selected with YRT_LIB_DIR
     _sig(dev, "yrtDenoiseDefaults", i32, C.POINTER(DenoiseParams))
     _sig(dev, "yrtDenoiseFrameBuffer", i32, vp, vp, vp, vp, C.POINTER(DenoiseParams))
     _sig(dev, "yrtGetDenoiseTimes", i32, vp, PF, PF)
+    _sig(dev, "yrtRenderAlbedo", i32, vp, vp, vp, i32, i32, vp)
 except AttributeError:
     pass
 _sig(dev, "yrtDebugDecodeImage", i32, cstr, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, sz)
