@@ -336,6 +336,17 @@ YRT_API int yrtDebugCheckMath(YRTDevice dev, int fn, uint64_t* out2);
  * reconstruction from table2048 (the 12-bit mantissas of tests/golden/sse_rcp_tables.json) for
  * all 2^32 inputs. out2 as yrtDebugCheckMath. */
 YRT_API int yrtDebugCheckMathTable(YRTDevice dev, int fn, const uint16_t* table2048, uint64_t* out2);
+/* Test-only probe of the device's shading layer (k_check_shade, kernels/k_aux.h): runs the
+ * kernels' own BRDF component, CompositedBRDF, camera and light functions on n rows, so that
+ * tests can compare them with the reference's classes bit for bit. rows: n x 48 words (wo, Ns, Ng,
+ * Tx, Ty, wi, s.xy, ss, component count, 2 pad, 3 x (kind, R.rgb, a, b, c, pad)); out: n x 12
+ * words. mode 0: component 0's eval at wi and sample at s (eval, sample, wi, pdf); mode 1: the
+ * set's sample at (s, ss) (colour, wi, pdf, type); mode 2: object = a committed camera, pixel =
+ * wo.xy, lens = s (org, dir); mode 3: object = a light primitive, P = wo, frame Ns (L, wi, pdf).
+ * materials: numMaterials device material records (128 B each) that conductor components index
+ * with c; every index in the rows is checked before the launch. Not part of the renderer. */
+YRT_API int yrtDebugShade(YRTDevice dev, int mode, YRTHandle object, const float* rows, int n, const void* materials,
+                          int numMaterials, float* out);
 /* The image tile that logical tile t of a sharded job's frame of T tiles covers
  * (common/yrt_tile_scatter.h: a fixed bijection of [0, T), used by the renderer and the gather
  * whenever the tile stride is above 1). Host-side; -1 for t outside [0, T). */

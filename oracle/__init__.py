@@ -25,6 +25,7 @@ if not LIB.exists():
     build()
 REF_LIB = HERE / "_ref" / "libref_kat.so"  # reference-compiled KAT library (make -C oracle ref)
 REF_MATH_LIB = HERE / "_ref" / "libref_math.so"  # the reference's common/math, compiled (make -C oracle ref)
+REF_SHADE_LIB = HERE / "_ref" / "libref_shade.so"  # its cameras, BRDFs and CompositedBRDF (make -C oracle ref)
 IEEE_LIB = HERE / "liboracle_ieee.so"  # rcp = 1/x, rsqrt = 1/sqrt(x): tools/rcp_sensitivity.py only
 _lib = C.CDLL(str(LIB))
 
@@ -64,6 +65,12 @@ _sig("oracle_libm", None, i32, i32, vp, vp, vp)
 _sig("oracle_vecmath", None, i32, i32, vp, vp, vp)
 _sig("oracle_bsphere", None, i32, vp, vp, vp, vp, vp)
 _sig("oracle_camera_rays", i32, vp, sz, i32, vp, vp, vp)
+_sig("oracle_camera_rays_lens", i32, vp, sz, i32, vp, vp, vp, vp)
+_sig("oracle_brdf_comps", i32, i32, vp, i32, vp)
+_sig("oracle_brdf", i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp)
+_sig("oracle_material_components", i32, vp, sz, vp, i32, vp, vp)
+_sig("oracle_light_sample", i32, vp, sz, vp, i32, vp, vp, vp, vp, vp, vp)
+_sig("oracle_brdf_set_sample", i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp)
 
 
 def _err():
@@ -239,6 +246,84 @@ def camera_rays(blob: bytes, px):
     if _lib.oracle_camera_rays(blob, len(blob), px.shape[0], px.ctypes.data, org.ctypes.data, dir_.ctypes.data):
         raise RuntimeError(f"oracle_camera_rays: {_err()}")
     return org, dir_
+
+
+def _f32(a, *shape):
+    return np.ascontiguousarray(a, np.float32).reshape(*shape)
+
+
+def camera_rays_lens(blob: bytes, px, lens):
+    """camera_rays with a lens sample (n, 2) per row (the depth-of-field camera)."""
+    px, lens = _f32(px, -1, 2), _f32(lens, -1, 2)
+    org = np.zeros((px.shape[0], 3), np.float32)
+    dir_ = np.zeros_like(org)
+    if _lib.oracle_camera_rays_lens(blob, len(blob), px.shape[0], px.ctypes.data, lens.ctypes.data, org.ctypes.data,
+                                    dir_.ctypes.data):
+        raise RuntimeError(f"oracle_camera_rays_lens: {_err()}")
+    return org, dir_
+
+
+def brdf_comps(kind, args):
+    """(n, 6) = R.rgb, a, b, c: the component record the constructor arguments args (n, 16) make."""
+    args = _f32(args, -1, 16)
+    out = np.zeros((args.shape[0], 6), np.float32)
+    if _lib.oracle_brdf_comps(kind, args.ctypes.data, args.shape[0], out.ctypes.data):
+        raise RuntimeError(f"oracle_brdf_comps: {_err()}")
+    return out
+
+
+def brdf(kind, args, wo, Ns, Ng, Tx, Ty, wi, s):
+    """BRDF::eval at wi and BRDF::sample at s of component `kind` per row: eval, sample (n, 3),
+    sampled wi (n, 3), pdf (n)."""
+    args = _f32(args, -1, 16)
+    n = args.shape[0]
+    v = [_f32(x, n, 3) for x in (wo, Ns, Ng, Tx, Ty, wi)]
+    s = _f32(s, n, 2)
+    ev, sa, wo_ = (np.zeros((n, 3), np.float32) for _ in range(3))
+    pdf = np.zeros(n, np.float32)
+    if _lib.oracle_brdf(kind, args.ctypes.data, n, *[x.ctypes.data for x in v], s.ctypes.data, ev.ctypes.data,
+                        sa.ctypes.data, wo_.ctypes.data, pdf.ctypes.data):
+        raise RuntimeError(f"oracle_brdf: {_err()}")
+    return ev, sa, wo_, pdf
+
+
+def brdf_set_sample(kinds, args, wo, frame, s, ss):
+    """CompositedBRDF::sample over the components `kinds` (<= 3): color, wi (n, 3), pdf (n), type (n)."""
+    kinds = np.ascontiguousarray(kinds, np.int32)
+    args = _f32(args, -1, len(kinds), 16)
+    n = args.shape[0]
+    wo, frame, s, ss = _f32(wo, n, 3), _f32(frame, n, 12), _f32(s, n, 2), _f32(ss, n)
+    col, wi = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    pdf, typ = np.zeros(n, np.float32), np.zeros(n, np.uint32)
+    if _lib.oracle_brdf_set_sample(len(kinds), kinds.ctypes.data, args.ctypes.data, n, wo.ctypes.data,
+                                   frame.ctypes.data, s.ctypes.data, ss.ctypes.data, col.ctypes.data, wi.ctypes.data,
+                                   pdf.ctypes.data, typ.ctypes.data):
+        raise RuntimeError(f"oracle_brdf_set_sample: {_err()}")
+    return col, wi, pdf, typ
+
+
+def material_components(blob: bytes, medium4, rows):
+    """Material::shade of the blob's material in the medium (T.rgb, eta) on rows (n, 20) = wo, Ns, Ng,
+    Tx, Ty, wi, s: (n, 34) = count, then 3 x (type bits, eval3, sample3, wi3, pdf)."""
+    rows, medium4 = _f32(rows, -1, 20), _f32(medium4, 4)
+    out = np.zeros((rows.shape[0], 34), np.float32)
+    if _lib.oracle_material_components(blob, len(blob), medium4.ctypes.data, rows.shape[0], rows.ctypes.data,
+                                       out.ctypes.data):
+        raise RuntimeError(f"oracle_material_components: {_err()}")
+    return out
+
+
+def light_sample(blob: bytes, xfm12, P, Ns, s):
+    """Light::sample of the blob's light placed with xfm12, at shade points P (n, 3) with normal
+    Ns and samples s (n, 2): L, wi (n, 3), pdf (n)."""
+    P = _f32(P, -1, 3)
+    n = P.shape[0]
+    xfm12, Ns, s = _f32(xfm12, 12), _f32(Ns, n, 3), _f32(s, n, 2)
+    L, wi, pdf = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+    if _lib.oracle_light_sample(blob, len(blob), xfm12.ctypes.data, n, P.ctypes.data, Ns.ctypes.data, s.ctypes.data,
+                                L.ctypes.data, wi.ctypes.data, pdf.ctypes.data):
+        raise RuntimeError(f"oracle_light_sample: {_err()}")
+    return L, wi, pdf
 
 
 def permutations(size, seed, count):

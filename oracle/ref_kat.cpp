@@ -7,7 +7,8 @@
 //   common/sys/platform.cpp    alignedMalloc/alignedFree used by vector_t
 // Everything else the reference's sampler needs (devices/device_singleray/default.h, the
 // filter's Distribution2D) pulls in common/simd, which does not compile with g++
-// (common/simd/sseb.h:108), so it cannot be built here.
+// (common/simd/sseb.h:108). clang builds it with one rename: oracle/ref_shade.cpp
+// runs the real SamplerFactory::init with the B-spline filter (ref_sample_table there).
 //
 // The loops below are this build's own driver code around those reference types: they are
 // the call patterns of integratorrenderer.cpp:134,149 (per-tile set draw) and of

@@ -1823,7 +1823,8 @@ static V3 brdf_sample(const Brdf* c, V3 wo, const DG* dg, float sx, float sy, V3
       const float alpha = c->b * rcp(ct);
       float cT;
       const V3 la = muls(c->R, alpha);
-      return muls(v3(yrt_expf(la.x), yrt_expf(la.y), yrt_expf(la.z)), 1.f - fres2(ct, c->a, &cT));
+      /* exp(Color) is the SSE exp_ps (color_sse.h:216), not expf */
+      return muls(v3(yrt_exp_ps(la.x), yrt_exp_ps(la.y), yrt_exp_ps(la.z)), 1.f - fres2(ct, c->a, &cT));
     }
     case B_LAYER: { /* dielectriclayer.h:40-62 */
       float cO = dot(wo, dg->Ns);
@@ -2087,6 +2088,57 @@ static void shade(const World* W, const Material* m, Medium cur, DG* dg, BSet* s
   }
 }
 
+/* Light::sample of a light that is not presampled: the sampled direction, its pdf and the
+ * radiance; 0 where the reference returns zero radiance before it has a direction (a triangle
+ * light seen from behind). ls.tMax is not computed: the integrator replaces it
+ * (pathtraceintegrator.cpp, tMaxShadowRay). */
+static int light_sample(const Light* Lt, const DG* dgp, float sx, float sy, V3* wi_o, float* pdf_o, V3* Ls_o) {
+  const DG dg = *dgp;
+  V3 wi = vs(0.f), Ls = vs(0.f);
+  float pdf = 0.f;
+  if (Lt->type == LT_AMBIENT) { /* ambientlight.h:52-65 */
+    wi = cos_hemi(sx, sy, dg.Ns, &pdf);
+    Ls = Lt->L;
+  } else if (Lt->type == LT_TRIANGLE) { /* trianglelight.h:77-85 */
+    const float su = sqrtf(sx);
+    const V3 d = sub(add(add(Lt->v2, muls(sub(Lt->v0, Lt->v2), 1.0f - su)), muls(sub(Lt->v1, Lt->v2), sy * su)), dg.P);
+    const float tMax = length(d);
+    const float dDotNg = dot(d, Lt->Ng);
+    if (dDotNg >= 0) return 0;
+    wi = muls(d, rcp(tMax));
+    pdf = 2.0f * tMax * tMax * tMax * rcp(fabsf(dDotNg));
+    Ls = Lt->L;
+  } else if (Lt->type == LT_POINT) { /* pointlight.h:36-42 */
+    const V3 d = sub(Lt->P, dg.P);
+    const float dist = length(d);
+    wi = divs(d, dist);
+    pdf = dist * dist;
+    Ls = Lt->L;
+  } else if (Lt->type == LT_SPOT) { /* spotlight.h:41-52 */
+    const V3 d = sub(Lt->P, dg.P);
+    const float dist = length(d);
+    wi = muls(d, rcp(dist));
+    pdf = dist * dist;
+    const float ca = dot(wi, Lt->D);
+    if (Lt->cosMin != Lt->cosMax) Ls = muls(Lt->L, clamp01((ca - Lt->cosMax) * rcp(Lt->cosMin - Lt->cosMax)));
+    else Ls = ca > Lt->cosMin ? Lt->L : vs(0.f);
+  } else if (Lt->type == LT_DIRECTIONAL) { /* directionallight.h:31-33 */
+    wi = Lt->D;
+    pdf = 1.0f;
+    Ls = Lt->L;
+  } else if (Lt->type == LT_DISTANT) { /* distantlight.h:46-50, shapesampler.h:149-165 */
+    const float ang = Lt->halfAngle;
+    const float phi = TWO_PI_F * sx;
+    const float cT = 1.0f - sy * (1.0f - yrt_cosf(ang));
+    const float sT = sqrtf(fmaxf(0.0f, 1.0f - cT * cT));
+    pdf = rcp(4.0f * PI_F * (yrt_sinf(0.5f * ang) * yrt_sinf(0.5f * ang)));
+    wi = lmul(frame_(Lt->D), v3(yrt_cosf(phi) * sT, yrt_sinf(phi) * sT, cT));
+    Ls = Lt->L;
+  }
+  *wi_o = wi; *pdf_o = pdf; *Ls_o = Ls;
+  return 1;
+}
+
 /* HDRILight::Le (lights/hdrilight.cpp:43-71) */
 static V3 hdri_Le(const World* W, const Light* L, V3 wo) {
   const V3 wi = xfmVector(L->w2l, neg(wo));
@@ -2216,45 +2268,8 @@ static V3 Li(const World* W, const RCfg* R, const Table* T, int rec, Ray ray, ui
           wi = v3(ls[0], ls[1], ls[2]);
           pdf = ls[3];
           Ls = v3(ls[4], ls[5], ls[6]);
-        } else if (Lt->type == LT_AMBIENT) { /* ambientlight.h:52-65 */
-          wi = cos_hemi(S2X(0), S2Y(0), dg.Ns, &pdf);
-          Ls = Lt->L;
-        } else if (Lt->type == LT_TRIANGLE) { /* trianglelight.h:77-85 */
-          const float sx = S2X(0), sy = S2Y(0);
-          const float su = sqrtf(sx);
-          const V3 d = sub(add(add(Lt->v2, muls(sub(Lt->v0, Lt->v2), 1.0f - su)), muls(sub(Lt->v1, Lt->v2), sy * su)), dg.P);
-          const float tMax = length(d);
-          const float dDotNg = dot(d, Lt->Ng);
-          if (dDotNg >= 0) continue; /* returns zero radiance */
-          wi = muls(d, rcp(tMax));
-          pdf = 2.0f * tMax * tMax * tMax * rcp(fabsf(dDotNg));
-          Ls = Lt->L;
-        } else if (Lt->type == LT_POINT) { /* pointlight.h:36-42 */
-          const V3 d = sub(Lt->P, dg.P);
-          const float dist = length(d);
-          wi = divs(d, dist);
-          pdf = dist * dist;
-          Ls = Lt->L;
-        } else if (Lt->type == LT_SPOT) { /* spotlight.h:41-52 */
-          const V3 d = sub(Lt->P, dg.P);
-          const float dist = length(d);
-          wi = muls(d, rcp(dist));
-          pdf = dist * dist;
-          const float ca = dot(wi, Lt->D);
-          if (Lt->cosMin != Lt->cosMax) Ls = muls(Lt->L, clamp01((ca - Lt->cosMax) * rcp(Lt->cosMin - Lt->cosMax)));
-          else Ls = ca > Lt->cosMin ? Lt->L : vs(0.f);
-        } else if (Lt->type == LT_DIRECTIONAL) { /* directionallight.h:31-33 */
-          wi = Lt->D;
-          pdf = 1.0f;
-          Ls = Lt->L;
-        } else if (Lt->type == LT_DISTANT) { /* distantlight.h:46-50, shapesampler.h:149-165 */
-          const float ang = Lt->halfAngle;
-          const float phi = TWO_PI_F * S2X(0);
-          const float cT = 1.0f - S2Y(0) * (1.0f - yrt_cosf(ang));
-          const float sT = sqrtf(fmaxf(0.0f, 1.0f - cT * cT));
-          pdf = rcp(4.0f * PI_F * (yrt_sinf(0.5f * ang) * yrt_sinf(0.5f * ang)));
-          wi = lmul(frame_(Lt->D), v3(yrt_cosf(phi) * sT, yrt_sinf(phi) * sT, cT));
-          Ls = Lt->L;
+        } else if (!light_sample(Lt, &dg, S2X(0), S2Y(0), &wi, &pdf, &Ls)) {
+          continue; /* returns zero radiance */
         }
         if (v3zero(Ls) || pdf == 0.f) continue;
         const V3 brdf = bs_eval(&bs, wo, &dg, wi, BT_DIFFUSE);
@@ -2408,18 +2423,180 @@ static void* worker(void* arg) {
 /* DebugRenderer::RenderJob::renderTile (debugrenderer.cpp:66-140) */
 /* The frame blob's camera rays for pixel coordinates px[2i] = fx, px[2i+1] = fy (lens sample 0):
  * org[3i], dir[3i]. For the pin of the camera path against the reference's own operations. */
-int oracle_camera_rays(const void* blob, size_t bytes, int n, const float* px, float* org, float* dir) {
+int oracle_camera_rays_lens(const void* blob, size_t bytes, int n, const float* px, const float* lens, float* org,
+                            float* dir) {
   Blob B;
   if (blob_parse(blob, bytes, &B)) return -1;
   Camera C;
   if (camera_build(&B, &C)) { blob_free(&B); return -1; }
   for (int i = 0; i < n; ++i) {
     V3 o, d;
-    camera_ray(&C, px[2 * i], px[2 * i + 1], 0.f, 0.f, &o, &d);
+    camera_ray(&C, px[2 * i], px[2 * i + 1], lens ? lens[2 * i] : 0.f, lens ? lens[2 * i + 1] : 0.f, &o, &d);
     org[3 * i] = o.x; org[3 * i + 1] = o.y; org[3 * i + 2] = o.z;
     dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z;
   }
   blob_free(&B);
+  return 0;
+}
+int oracle_camera_rays(const void* blob, size_t bytes, int n, const float* px, float* org, float* dir) {
+  return oracle_camera_rays_lens(blob, bytes, n, px, NULL, org, dir);
+}
+
+/* ---- the shading layer's twins of oracle/ref_shade.cpp (tests/test_ref_shade.py): thin wrappers
+ * over brdf_eval / brdf_sample / bs_sample / light_build / light_sample, with no arithmetic of
+ * their own beyond what the reference's constructors do with their arguments. */
+static const uint32_t kBrdfType[16] = {0x1u, 0x100u, 0x01000000u, 0x01000000u, 0x1u, 0x10u, 0x01000000u, 0x10u,
+                                       0x100u, 0x100u, 0x10u, 0x10u, 0x1u, 0x1u, 0x01000000u, 0x10u};
+/* args[16] = R.rgb, p0, p1, p2, eta.rgb, k.rgb, pad: the constructor arguments of the component's
+ * reference class -> the record `shade` would add (the constructors' own derived members) */
+static int brdf_from_args(int kind, const float* p, Brdf* b) {
+  if (kind < 0 || kind > 15) return -1;
+  memset(b, 0, sizeof(*b));
+  b->kind = kind;
+  b->type = kBrdfType[kind];
+  b->R = v3(p[0], p[1], p[2]);
+  b->eta = v3(p[6], p[7], p[8]);
+  b->k = v3(p[9], p[10], p[11]);
+  switch (kind) {
+    case B_DIEL_REFL: b->a = p[3] * rcp(p[4]); b->b = p[5]; break;            /* dielectric.h:33-34 */
+    case B_CONST_TRANS: b->R = vs(p[3]); break;                               /* dielectric.h:177-178 */
+    case B_THIN_TRANS:                                                        /* dielectric.h:121-122 */
+      b->R = v3(yrt_logf(p[0]), yrt_logf(p[1]), yrt_logf(p[2]));
+      b->a = p[3] * rcp(p[4]); b->b = p[5];
+      break;
+    case B_LAYER: b->a = p[3] * rcp(p[4]); b->b = p[4] * rcp(p[3]); break;    /* dielectriclayer.h:39-40 */
+    case B_MICRO: b->a = p[3]; b->b = p[4]; b->c = p[5]; break;
+    case B_SPEC: case B_MICRO_COND: case B_MINNAERT: case B_VELVETY: b->a = p[3]; break;
+    case B_MICRO_ANISO: b->a = p[3]; b->b = p[4]; break;
+    case B_DIEL_TRANS: b->a = p[3] * rcp(p[4]); break;                        /* dielectric.h:75-76 */
+    case B_LAYER_GLITTER: b->a = p[3] * rcp(p[4]); b->b = p[4] * rcp(p[3]); b->c = p[5]; break;
+    default: break;
+  }
+  return 0;
+}
+static void dg_from(DG* dg, const float* Ns, const float* Ng, const float* Tx, const float* Ty) {
+  memset(dg, 0, sizeof(*dg));
+  dg->Ns = v3(Ns[0], Ns[1], Ns[2]);
+  dg->Ng = v3(Ng[0], Ng[1], Ng[2]);
+  dg->Tx = v3(Tx[0], Tx[1], Tx[2]);
+  dg->Ty = v3(Ty[0], Ty[1], Ty[2]);
+}
+static void put3(float* o, V3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+
+/* the component records (R.rgb, a, b, c) the arguments make: what the device probe is handed */
+int oracle_brdf_comps(int kind, const float* args, int n, float* comp6) {
+  for (int i = 0; i < n; ++i) {
+    Brdf b;
+    if (brdf_from_args(kind, args + 16 * i, &b)) return fail("component kind out of range");
+    put3(comp6 + 6 * i, b.R);
+    comp6[6 * i + 3] = b.a; comp6[6 * i + 4] = b.b; comp6[6 * i + 5] = b.c;
+  }
+  return 0;
+}
+int oracle_brdf(int kind, const float* args, int n, const float* wo, const float* Ns, const float* Ng, const float* Tx,
+                const float* Ty, const float* wi, const float* s, float* eval3, float* sample3, float* wi_out3,
+                float* pdf) {
+  for (int i = 0; i < n; ++i) {
+    Brdf b;
+    if (brdf_from_args(kind, args + 16 * i, &b)) return fail("component kind out of range");
+    DG dg;
+    dg_from(&dg, Ns + 3 * i, Ng + 3 * i, Tx + 3 * i, Ty + 3 * i);
+    const V3 o = v3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
+    put3(eval3 + 3 * i, brdf_eval(&b, o, &dg, v3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2])));
+    V3 w;
+    put3(sample3 + 3 * i, brdf_sample(&b, o, &dg, s[2 * i], s[2 * i + 1], &w, &pdf[i]));
+    put3(wi_out3 + 3 * i, w);
+  }
+  return 0;
+}
+/* Material::shade of the blob's first material object in the current medium (T.rgb, eta), read
+ * back as oracle/ref_shade.cpp's ref_material_components does: rows n x 20 = wo, Ns, Ng, Tx, Ty, wi,
+ * s.xy; out n x 34 = component count, then 3 x (type bits, eval3, sample3, wi3, pdf). */
+int oracle_material_components(const void* blob, size_t bytes, const float* medium4, int n, const float* rows,
+                               float* out) {
+  Blob B;
+  if (blob_parse(blob, bytes, &B)) return -1;
+  int oi = -1;
+  for (int i = 0; i < B.nobj && oi < 0; ++i)
+    if (B.objs[i].kind == K_MATERIAL) oi = i;
+  Material m;
+  mat_build(&B, oi, &m);
+  if (m.type == MT_NONE) { blob_free(&B); return fail("no material the oracle knows"); }
+  World W;
+  memset(&W, 0, sizeof(W));
+  W.blob = &B;
+  const Medium cur = {v3(medium4[0], medium4[1], medium4[2]), medium4[3]};
+  int rc = 0;
+  for (int i = 0; i < n && !rc; ++i) {
+    const float* r = rows + 20 * i;
+    float* o = out + 34 * i;
+    memset(o, 0, 34 * sizeof(float));
+    DG dg;
+    dg_from(&dg, r + 3, r + 6, r + 9, r + 12);
+    const V3 wo = v3(r[0], r[1], r[2]);
+    BSet bs;
+    shade(&W, &m, cur, &dg, &bs);
+    if (bs.n > 3) { rc = fail("more than 3 components"); break; }
+    const int32_t count = bs.n;
+    memcpy(o, &count, 4);
+    for (int k = 0; k < bs.n; ++k) {
+      float* c = o + 1 + 11 * k;
+      memcpy(c, &bs.c[k].type, 4);
+      put3(c + 1, brdf_eval(&bs.c[k], wo, &dg, v3(r[15], r[16], r[17])));
+      V3 w;
+      put3(c + 4, brdf_sample(&bs.c[k], wo, &dg, r[18], r[19], &w, &c[10]));
+      put3(c + 7, w);
+    }
+  }
+  blob_free(&B);
+  return rc;
+}
+
+/* Light::sample of the blob's first light object placed with transform xfm12 (Light::transform),
+ * at the shade points P with shading normal Ns (the ambient light samples about it): L, wi, pdf.
+ * A triangle light seen from behind gives L = 0, wi = 0, pdf = 0. */
+int oracle_light_sample(const void* blob, size_t bytes, const float* xfm12, int n, const float* P, const float* Ns,
+                        const float* s, float* L3, float* wi3, float* pdf) {
+  Blob B;
+  if (blob_parse(blob, bytes, &B)) return -1;
+  int oi = -1;
+  for (int i = 0; i < B.nobj && oi < 0; ++i)
+    if (B.objs[i].kind == K_LIGHT) oi = i;
+  Light L;
+  Mesh* shape = NULL;
+  if (oi < 0 || light_build(&B, oi, a3_from12(xfm12), -1, -1, &L, &shape)) { blob_free(&B); return fail("no light the oracle knows"); }
+  if (shape) mesh_free(shape);
+  for (int i = 0; i < n; ++i) {
+    DG dg;
+    memset(&dg, 0, sizeof(dg));
+    dg.P = v3(P[3 * i], P[3 * i + 1], P[3 * i + 2]);
+    dg.Ns = dg.Ng = v3(Ns[3 * i], Ns[3 * i + 1], Ns[3 * i + 2]);
+    V3 wi = vs(0.f), Ls = vs(0.f);
+    pdf[i] = 0.f;
+    if (!light_sample(&L, &dg, s[2 * i], s[2 * i + 1], &wi, &pdf[i], &Ls)) { wi = Ls = vs(0.f); pdf[i] = 0.f; }
+    put3(L3 + 3 * i, Ls);
+    put3(wi3 + 3 * i, wi);
+  }
+  free(L.ycdf); free(L.ypdf); free(L.xcdf); free(L.xpdf);
+  blob_free(&B);
+  return 0;
+}
+int oracle_brdf_set_sample(int nk, const int32_t* kinds, const float* args, int n, const float* wo, const float* frame,
+                           const float* s, const float* ss, float* color3, float* wi3, float* pdf, uint32_t* type) {
+  if (nk < 1 || nk > 3) return fail("1..3 components");
+  for (int i = 0; i < n; ++i) {
+    BSet bs;
+    bs.n = nk;
+    for (int k = 0; k < nk; ++k)
+      if (brdf_from_args(kinds[k], args + ((size_t)i * nk + k) * 16, &bs.c[k])) return fail("component kind out of range");
+    DG dg;
+    const float* f = frame + 12 * i;
+    dg_from(&dg, f, f + 3, f + 6, f + 9);
+    V3 w;
+    put3(color3 + 3 * i, bs_sample(&bs, v3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]), &dg, s[2 * i], s[2 * i + 1], ss[i],
+                                   &w, &pdf[i], &type[i]));
+    put3(wi3 + 3 * i, w);
+  }
   return 0;
 }
 

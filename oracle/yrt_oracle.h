@@ -106,6 +106,31 @@ void oracle_libm(int fn, int n, const float* x, const float* y, float* out);
 void oracle_vecmath(int fn, int n, const float* a, const float* b, float* out);
 void oracle_bsphere(int n, const float* lo, const float* hi, const float* org, const float* dir, float* out);
 int oracle_camera_rays(const void* blob, size_t bytes, int n, const float* px, float* org, float* dir);
+/* the same with a lens sample per row (lens n x 2, NULL: 0): the depth-of-field camera */
+int oracle_camera_rays_lens(const void* blob, size_t bytes, int n, const float* px, const float* lens, float* org,
+                            float* dir);
+/* The shading layer's entry points, the twins of oracle/ref_shade.cpp's (the reference's own
+ * classes): thin wrappers over the static BRDF component eval / sample and the CompositedBRDF
+ * sampler. args n x 16 = R.rgb, p0, p1, p2, eta.rgb, k.rgb, pad: the constructor arguments of the
+ * class named at kernels/yrt_shade.h CompKind `kind`; the vectors n x 3, s n x 2.
+ * oracle_brdf_comps: the (R.rgb, a, b, c) record those arguments make (the device's Comp). */
+int oracle_brdf_comps(int kind, const float* args, int n, float* comp6);
+int oracle_brdf(int kind, const float* args, int n, const float* wo, const float* Ns, const float* Ng, const float* Tx,
+                const float* Ty, const float* wi, const float* s, float* eval3, float* sample3, float* wi_out3,
+                float* pdf);
+/* Material::shade of the blob's first material object in the current medium (T.rgb, eta): rows
+ * n x 20 = wo, Ns, Ng, Tx, Ty, wi, s.xy; out n x 34 = component count, then 3 x (type bits, the
+ * component's eval at wi, its sample at s, the sampled wi, pdf) */
+int oracle_material_components(const void* blob, size_t bytes, const float* medium4, int n, const float* rows,
+                               float* out);
+/* Light::sample of the blob's first light object after Light::transform(xfm12), at shade points P
+ * (n x 3) with shading normal Ns and samples s (n x 2): L, wi (n x 3), pdf (n) */
+int oracle_light_sample(const void* blob, size_t bytes, const float* xfm12, int n, const float* P, const float* Ns,
+                        const float* s, float* L3, float* wi3, float* pdf);
+/* CompositedBRDF::sample over nk <= 3 components per row: args n x nk x 16, frame n x 12 = Ns, Ng,
+ * Tx, Ty, ss n */
+int oracle_brdf_set_sample(int nk, const int32_t* kinds, const float* args, int n, const float* wo, const float* frame,
+                           const float* s, const float* ss, float* color3, float* wi3, float* pdf, uint32_t* type);
 void oracle_permutations(int size, int seed, int count, int32_t* out);
 void oracle_shuffles(int n, int seed, int count, uint32_t* out);
 /* SamplerFactory::init sample table: dims as in the GPU table ([dim][set*spp+s]);

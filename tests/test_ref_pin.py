@@ -6,7 +6,9 @@ common/sys/platform.cpp (where they lie under /root/reference) behind the small 
 oracle/ref_kat.cpp. These tests compare the C restatement (oracle/yrt_oracle.c) with it bit for
 bit: Random (KAT 1), Permutation, vector_t::shuffle, the per-tile set draw of
 integratorrenderer.cpp:134,149, and SamplerFactory::init tables without the pixel filter
-(the filter's Distribution2D lives behind default.h, which does not compile here).
+and, through oracle/_ref/libref_shade.so (oracle/ref_shade.cpp: default.h compiles with one rename),
+the tables with the B-spline pixel filter from the reference's real SamplerFactory::init. That
+library also pins the cameras, BRDFs and lights (tests/test_ref_shade.py).
 """
 import ctypes as C
 
@@ -19,6 +21,7 @@ if not oracle.REF_LIB.exists():
     pytest.skip("oracle/_ref not built (needs /root/reference: make -C oracle ref)", allow_module_level=True)
 
 _ref = C.CDLL(str(oracle.REF_LIB))
+
 SEEDS = [1, 27, 5897, 91711, 81551, 2 * 5897, 123456789, -7, 0]
 
 
@@ -118,6 +121,37 @@ def _vectors(seed, n=1 << 16):
     v[: n // 16] = np.float32(rng.integers(-2, 3, (n // 16, 3)))
     v[n // 16: n // 8] = rng.choice(np.array([0.0, -0.0, 1.0, -1.0, 0.5], np.float32), (n // 16, 3))
     return v
+
+
+# ---------------------------------------------------------------- the filtered table (libref_shade.so)
+# oracle/ref_shade.cpp drives the reference's real SamplerFactory::init with its BSplineFilter,
+# Distribution2D and filter.cpp (Distribution1D normalizes with rcp: an Intel host for the live
+# comparison). The filter warps the pixel dims only; the fixture holds those two rows per shape.
+import ref_shade_cases as RS  # noqa: E402
+
+_shade = C.CDLL(str(oracle.REF_SHADE_LIB)) if oracle.REF_SHADE_LIB.exists() else None
+
+
+def _table_fixture(spp, iteration, n1, n2):
+    f = np.load(Path(__file__).resolve().parent / "golden" / "ref_shade_table.npz")
+    name = f"spp{spp}_it{iteration}_{n1}_{n2}"
+    assert np.array_equal(f[name + ".digest"], RS.digest(np.array([spp, 64, iteration, n1, n2], np.int32)))
+    return f[name]
+
+
+@pytest.mark.skipif(_shade is None, reason="oracle/_ref/libref_shade.so not built (make -C oracle ref)")
+@intel_only
+@pytest.mark.parametrize("spp,iteration,n1,n2", RS.TABLE_SHAPES)
+def test_sample_tables_with_the_bspline_filter(spp, iteration, n1, n2):
+    """SamplerFactory::init(iteration, BSplineFilter) itself, every dim, against the oracle's table;
+    and without a filter, against ref_kat.cpp's replayed call pattern's twin."""
+    for bspline in (True, False):
+        ref = RS.ref_sample_table(_shade, spp, 64, iteration, n1, n2, bspline)
+        got = oracle.sample_table(spp, 64, iteration, n1, n2, filter="bspline" if bspline else "none")
+        assert np.array_equal(ref.view(np.uint32), got.view(np.uint32)), bspline
+        if bspline:
+            assert np.array_equal(_table_fixture(spp, iteration, n1, n2).view(np.uint32), ref[:2].view(np.uint32))
+    print(f"sample table spp {spp} iteration {iteration}: {ref.size} words compared twice")
 
 
 @needs_math

@@ -102,6 +102,43 @@ YRT_LIBM_FN float yrt_expf(float x) {
   return yrt_lm_ldexp(p, (int)n);
 }
 
+/* ---- Color exp: the reference's exp(Color) is not the C runtime's expf but the SSE polynomial
+ * exp_ps, lane by lane (common/math/color_sse.h:216 -> common/simd/sse_special.h:264-339): clamp
+ * to +-88.3762626647949 (min_ps / max_ps return their second operand for a NaN), n = floor(x
+ * log2(e) + 0.5) through a truncating conversion, r = x - n C1 - n C2, the Cephes polynomial in
+ * separate multiplies and adds (the SSE code has no fused ones), times 2^n built in the exponent
+ * field (n = -127 gives 0, n = 128 infinity). IEEE operations only, so the same bits everywhere. */
+YRT_LIBM_FN float yrt_exp_ps(float x) {
+  x = x < 88.3762626647949f ? x : 88.3762626647949f;
+  x = x > -88.3762626647949f ? x : -88.3762626647949f;
+  float fx = x * 1.44269504088896341f;
+  fx = fx + 0.5f;
+  const int32_t t = (int32_t)fx;
+  float tmp = (float)t;
+  fx = tmp - (tmp > fx ? 1.0f : 0.0f);
+  tmp = fx * 0.693359375f;
+  float z = fx * -2.12194440e-4f;
+  x = x - tmp;
+  x = x - z;
+  z = x * x;
+  float y = 1.9875691500e-4f;
+  y = y * x;
+  y = y + 1.3981999507e-3f;
+  y = y * x;
+  y = y + 8.3334519073e-3f;
+  y = y * x;
+  y = y + 4.1665795894e-2f;
+  y = y * x;
+  y = y + 1.6666665459e-1f;
+  y = y * x;
+  y = y + 5.0000001201e-1f;
+  y = y * z;
+  y = y + x;
+  y = y + 1.0f;
+  const float pow2n = yrt_lm_float((uint32_t)((int32_t)fx + 127) << 23);
+  return y * pow2n;
+}
+
 /* ---- log: x = m 2^e, m in [sqrt(1/2), sqrt(2)) */
 YRT_LIBM_FN float yrt_logf(float x) {
   if (x != x || x < 0.0f) return yrt_lm_float(0x7fc00000u);

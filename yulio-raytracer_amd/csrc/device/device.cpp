@@ -2305,6 +2305,34 @@ int yrtDebugCheckMathTable(YRTDevice dev, int fn, const uint16_t* table2048, uin
   DEV_END(-1)
 }
 
+int yrtDebugShade(YRTDevice dev, int mode, YRTHandle object, const float* rows, int n, const void* materials,
+                  int numMaterials, float* out) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  if (!D.gpu) throw std::runtime_error("yrtDebugShade: host-only device");
+  if (mode < 0 || mode > 3 || !rows || !out || n < 1) throw std::runtime_error("yrtDebugShade: invalid arguments");
+  const GpuCamera* cam = nullptr;
+  GpuLight light;
+  const GpuLight* lp = nullptr;
+  if (mode == 2) {
+    auto C = D.get<CameraObj>(object, "camera");
+    if (!C) throw std::runtime_error("yrtDebugShade: mode 2 takes a committed camera");
+    cam = &C->cam;
+  } else if (mode == 3) {
+    auto P = D.get<PrimitiveObj>(object, "primitive");
+    if (!P || !P->lightHandle || !P->lightHandle->inst)
+      throw std::runtime_error("yrtDebugShade: mode 3 takes a primitive of a committed light");
+    // the world-space light rtSetPrimitive would place in a scene
+    light = gpu_light_record(*P->lightHandle->inst->transform(P->transform, P->illumMask, P->shadowMask));
+    lp = &light;
+  }
+  HIP_CHECK(hipSetDevice(D.hipDevice));
+  if (check_shade(mode, n, rows, (const GpuMaterial*)materials, numMaterials, cam, lp, out) != 0)
+    throw std::runtime_error("yrtDebugShade: invalid rows or a failed launch");
+  return 0;
+  DEV_END(-1)
+}
+
 int yrtDebugTileScatter(int t, int T) {
   if (T < 1 || t < 0 || t >= T) return -1;
   return yrt_tile_scatter(t, T);

@@ -44,6 +44,31 @@ static void bind_view(GpuScene& S) {
   v.hdriDist = nullptr;
 }
 
+// The device record of a world-space light, without the scene's own indices (image, precomputed
+// slot, environment list): what the light samplers read.
+GpuLight gpu_light_record(const LightInst& L) {
+  GpuLight g;
+  memset(&g, 0, sizeof(g));
+  g.type = L.type;
+  g.illumMask = L.illumMask;
+  g.shadowMask = L.shadowMask;
+  g.precomputed = -1;
+  g.L[0] = L.L.x; g.L[1] = L.L.y; g.L[2] = L.L.z;
+  auto st3 = [](float* d, V3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
+  st3(g.v0, L.v0); st3(g.v1, L.v1); st3(g.v2, L.v2);
+  st3(g.e1, L.e1); st3(g.e2, L.e2); st3(g.Ng, L.Ng);
+  auto stA = [](float* d, const A3& a) {
+    const float v[12] = {a.l.vx.x, a.l.vx.y, a.l.vx.z, a.l.vy.x, a.l.vy.y, a.l.vy.z,
+                         a.l.vz.x, a.l.vz.y, a.l.vz.z, a.p.x,    a.p.y,    a.p.z};
+    memcpy(d, v, sizeof(v));
+  };
+  stA(g.l2w, L.l2w);
+  stA(g.w2l, L.w2l);
+  g.bsphere[0] = L.type == LIGHT_SPOT ? L.cosAngleMin : L.halfAngle;
+  g.bsphere[1] = L.type == LIGHT_SPOT ? L.cosAngleMax : L.cosHalfAngle;
+  return g;
+}
+
 std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<ScenePrim>>& prims, int stackDepth,
                                           bool upload) {
   auto t0 = std::chrono::steady_clock::now();
@@ -140,25 +165,7 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
     const auto& p = prims[i];
     if (!p || !p->light) continue;
     const LightInst& L = *p->light;
-    GpuLight g;
-    memset(&g, 0, sizeof(g));
-    g.type = L.type;
-    g.illumMask = L.illumMask;
-    g.shadowMask = L.shadowMask;
-    g.precomputed = -1;
-    g.L[0] = L.L.x; g.L[1] = L.L.y; g.L[2] = L.L.z;
-    auto st3 = [](float* d, V3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
-    st3(g.v0, L.v0); st3(g.v1, L.v1); st3(g.v2, L.v2);
-    st3(g.e1, L.e1); st3(g.e2, L.e2); st3(g.Ng, L.Ng);
-    auto stA = [](float* d, const A3& a) {
-      const float v[12] = {a.l.vx.x, a.l.vx.y, a.l.vx.z, a.l.vy.x, a.l.vy.y, a.l.vy.z,
-                           a.l.vz.x, a.l.vz.y, a.l.vz.z, a.p.x,    a.p.y,    a.p.z};
-      memcpy(d, v, sizeof(v));
-    };
-    stA(g.l2w, L.l2w);
-    stA(g.w2l, L.w2l);
-    g.bsphere[0] = L.type == LIGHT_SPOT ? L.cosAngleMin : L.halfAngle;
-    g.bsphere[1] = L.type == LIGHT_SPOT ? L.cosAngleMax : L.cosHalfAngle;
+    GpuLight g = gpu_light_record(L);
     // EnvironmentLight subclasses (api/scene.h:76): ambient, HDRI, distant
     if (L.type == LIGHT_AMBIENT || L.type == LIGHT_HDRI || L.type == LIGHT_DISTANT) {
       g.isEnv = 1;

@@ -87,6 +87,10 @@ struct GpuScene {
   float bboxLo[3] = {0, 0, 0}, bboxHi[3] = {0, 0, 0};
 };
 
+// The device record of a world-space light without the scene's own indices (image, precomputed
+// slot): what the light samplers read. build_gpu_scene fills those in.
+GpuLight gpu_light_record(const LightInst& L);
+
 std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<ScenePrim>>& prims, int stackDepth,
                                           bool upload);
 // A copy of an uploaded scene's device buffers on another HIP device (peer copies over xGMI),

@@ -410,6 +410,81 @@ __global__ __launch_bounds__(256) void k_check_math_table(int fn, const uint16_t
   }
 }
 
+// ---------------------------------------------------------------- shading-layer probe
+// k_check_shade (yrtDebugShade, test-only): one thread per row calls the device functions of the
+// shading layer as they stand, so that their results can be compared bit for bit with the
+// reference's own classes (tests/test_ref_shade.py). It holds no formula of its own.
+//   rows  n x 48 words: wo, Ns, Ng, Tx, Ty, wi (3 each), s.xy, ss, the component count, 2 pad,
+//         then 3 components of 8 words: kind, R.rgb, a, b, c, pad (conductor kinds: c = the
+//         index of their record in mats, as Material::shade stores it)
+//   out   n x 12 words
+//   mode 0  comp_eval at wi and comp_sample at s of component 0: eval, sample, wi (3 each), pdf
+//   mode 1  set_sample of the components at (s, ss): colour, wi (3 each), pdf, type bits
+//   mode 2  camera_ray of *cam at pixel = wo.xy, lens = s: org, dir
+//   mode 3  light_sample of *light at P = wo on the frame Ns, with s: L, wi (3 each), pdf
+// Every-material component mask and every light type, as k_shade's widest instantiation. Off
+// the render loop: its state may live in scratch.
+#define YRT_SHADE_ROW 48
+#define YRT_SHADE_OUT 12
+__global__ __launch_bounds__(64) void k_check_shade(int mode, int n, const float* __restrict__ rows,
+                                                    const GpuMaterial* __restrict__ mats,
+                                                    const GpuCamera* __restrict__ cam,
+                                                    const GpuLight* __restrict__ light, float* __restrict__ out) {
+  __shared__ float st[21 * 64];  // set_sample's candidate slots, [21][64]
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr unsigned CM = comps_of(YRT_ALL_MATS);
+  const float* r = rows + (size_t)i * YRT_SHADE_ROW;
+  float* o = out + (size_t)i * YRT_SHADE_OUT;
+  const V3 wo = v3(r[0], r[1], r[2]), wi = v3(r[15], r[16], r[17]);
+  DG dg;
+  dg.P = wo;  // mode 3 only
+  dg.Ns = v3(r[3], r[4], r[5]);
+  dg.Ng = v3(r[6], r[7], r[8]);
+  dg.Tx = v3(r[9], r[10], r[11]);
+  dg.Ty = v3(r[12], r[13], r[14]);
+  dg.s = dg.t = dg.error = 0.f;
+  dg.material = dg.light = -1;
+  dg.illumMask = dg.shadowMask = -1;
+  dg_frame(dg);
+  const float sx = r[18], sy = r[19], ss = r[20];
+  BRDFSet bs;
+  bs.n = __float_as_int(r[21]);
+#pragma unroll
+  for (int k = 0; k < YRT_MAX_COMPS; ++k) {
+    const float* c = r + 24 + 8 * k;
+    bs.c[k].kind = __float_as_int(c[0]);
+    bs.c[k].R = v3(c[1], c[2], c[3]);
+    bs.c[k].a = c[4];
+    bs.c[k].b = c[5];
+    bs.c[k].c = c[6];
+  }
+  V3 a = v3s(0.f), b = v3s(0.f), w = v3s(0.f);
+  float pdf = 0.f;
+  if (mode == 0) {
+    a = comp_eval<CM>(bs.c[0], mats, wo, dg, wi);
+    b = comp_sample<CM>(bs.c[0], mats, wo, dg, sx, sy, w, pdf);
+    o[9] = pdf;
+    o[10] = o[11] = 0.f;
+  } else if (mode == 1) {
+    uint32_t type = 0;
+    a = set_sample<CM>(bs, mats, wo, dg, sx, sy, ss, b, pdf, type, st + threadIdx.x);
+    o[6] = pdf;
+    o[7] = __uint_as_float(type);
+    o[8] = o[9] = o[10] = o[11] = 0.f;
+  } else if (mode == 2) {
+    camera_ray(*cam, r[0], r[1], a, b, sx, sy);
+  } else {
+    a = light_sample<kAllLights>(*light, dg, sx, sy, b, pdf);
+    o[6] = pdf;
+    o[7] = o[8] = o[9] = o[10] = o[11] = 0.f;
+  }
+  o[0] = a.x; o[1] = a.y; o[2] = a.z;
+  o[3] = b.x; o[4] = b.y; o[5] = b.z;
+  if (mode == 0) { o[6] = w.x; o[7] = w.y; o[8] = w.z; }
+  if (mode == 2) o[6] = o[7] = o[8] = o[9] = o[10] = o[11] = 0.f;
+}
+
 // ---------------------------------------------------------------- BVH refit (faceCamera)
 // Per-face dynamic geometry (rtUpdatePrimitive of YULIO_CAMERA_ALIGNED_ meshes,
 // singleray_device.cpp:354-398) keeps the BVH topology and only moves vertices: the moved

@@ -16,6 +16,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <mutex>
 #include <set>
@@ -189,6 +190,55 @@ int check_math_table(int fn, const uint16_t* table2048, unsigned long long* host
   }
   (void)hipFree(t);
   (void)hipFree(d);
+  return rc;
+}
+
+int check_shade(int mode, int n, const float* rows, const GpuMaterial* mats, int numMats, const GpuCamera* cam,
+                const GpuLight* light, float* out) {
+  if (mode < 0 || mode > 3 || n < 1 || !rows || !out) return -1;
+  if ((mode == 2 && !cam) || (mode == 3 && !light)) return -1;
+  // every index the kernel follows is checked here: the component count and kinds, and the
+  // material record of a conductor component
+  for (int i = 0; i < n && mode < 2; ++i) {
+    const float* r = rows + (size_t)i * YRT_SHADE_ROW;
+    int nc;
+    memcpy(&nc, r + 21, 4);
+    if (nc < 1 || nc > YRT_MAX_COMPS) return -1;
+    for (int k = 0; k < nc; ++k) {
+      int kind, id;
+      memcpy(&kind, r + 24 + 8 * k, 4);
+      memcpy(&id, r + 24 + 8 * k + 6, 4);
+      if (kind < 0 || kind > C_DIEL_LAYER_GLITTER) return -1;
+      if ((kind == C_CONDUCTOR || kind == C_MICRO_COND || kind == C_MICRO_ANISO) && (!mats || id < 0 || id >= numMats))
+        return -1;
+    }
+  }
+  float *dRows = nullptr, *dOut = nullptr;
+  GpuMaterial* dMats = nullptr;
+  GpuCamera* dCam = nullptr;
+  GpuLight* dLight = nullptr;
+  const size_t rowBytes = (size_t)n * YRT_SHADE_ROW * sizeof(float), outBytes = (size_t)n * YRT_SHADE_OUT * sizeof(float);
+  int rc = 0;
+  if (hipMalloc(&dRows, rowBytes) != hipSuccess || hipMalloc(&dOut, outBytes) != hipSuccess ||
+      hipMalloc(&dMats, sizeof(GpuMaterial) * (size_t)(numMats > 0 ? numMats : 1)) != hipSuccess ||
+      hipMalloc(&dCam, sizeof(GpuCamera)) != hipSuccess || hipMalloc(&dLight, sizeof(GpuLight)) != hipSuccess)
+    rc = -1;
+  if (!rc && hipMemcpy(dRows, rows, rowBytes, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+  if (!rc && mats && numMats > 0 &&
+      hipMemcpy(dMats, mats, sizeof(GpuMaterial) * (size_t)numMats, hipMemcpyHostToDevice) != hipSuccess)
+    rc = -1;
+  if (!rc && cam && hipMemcpy(dCam, cam, sizeof(GpuCamera), hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+  if (!rc && light && hipMemcpy(dLight, light, sizeof(GpuLight), hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+  if (!rc) {
+    hipLaunchKernelGGL(k_check_shade, dim3((n + 63) / 64), dim3(64), 0, 0, mode, n, dRows, dMats, dCam, dLight, dOut);
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = -1;
+  }
+  (void)hipFree(dLight);
+  (void)hipFree(dCam);
+  (void)hipFree(dMats);
+  (void)hipFree(dOut);
+  (void)hipFree(dRows);
   return rc;
 }
 

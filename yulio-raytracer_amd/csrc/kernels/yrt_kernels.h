@@ -186,6 +186,10 @@ int debug_pixel_capture(int pixelId, int frame, float4* out, int capacity);
 // Arithmetic self-check of the correctly rounded fast reciprocal (rcp_rn): see k_aux.h
 int check_math(int fn, unsigned long long* host2);
 int check_math_table(int fn, const uint16_t* table2048, unsigned long long* host2);
+// Shading-layer probe (k_check_shade, k_aux.h; test-only): n rows of 48 words in, 12 words out,
+// host pointers; mats numMats records (may be null), cam / light one host record for modes 2 / 3
+int check_shade(int mode, int n, const float* rows, const GpuMaterial* mats, int numMats, const GpuCamera* cam,
+                const GpuLight* light, float* out);
 // Multi-GPU gather (device.cpp): the pixels of the tiles of one shard (job tile =
 // tileOffset + j * tileStride, j < numTiles, over numFrames stacked frames of tilesPerFrame
 // tiles) as a slab of numTiles * 256 elements in tile order j and scan order within the tile;

@@ -449,7 +449,8 @@ __device__ __forceinline__ V3 comp_sample(const Comp c, const GpuMaterial* __res
       const float alpha = c.b * rcpf_(cosTheta);
       float cosThetaT;
       V3 la = c.R * alpha;
-      return v3(yrt_expf(la.x), yrt_expf(la.y), yrt_expf(la.z)) * (1.f - fresnel2(cosTheta, c.a, &cosThetaT));
+      // exp(Color) is the SSE exp_ps (common/math/color_sse.h:216), not expf
+      return v3(yrt_exp_ps(la.x), yrt_exp_ps(la.y), yrt_exp_ps(la.z)) * (1.f - fresnel2(cosTheta, c.a, &cosThetaT));
     }
     case C_DIEL_LAYER_LAMB: {
       YRT_IF_NOT(C_DIEL_LAYER_LAMB) break;

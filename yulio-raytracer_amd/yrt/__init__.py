@@ -233,6 +233,18 @@ class Device:
     def rtCommit(self, h):
         self._rc(N.dev.yrtCommit(self.h, h), "rtCommit")
 
+    def debug_shade(self, mode, rows, materials=None, obj=None):
+        """yrtDebugShade, the test-only probe of the kernels' shading layer: rows float32 (n, 48),
+        materials a (m, 32) float32 view of 128-byte device material records, obj a camera (mode 2) or
+        a light primitive (mode 3). Returns float32 (n, 12)."""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 48)
+        out = np.zeros((rows.shape[0], 12), np.float32)
+        m = None if materials is None else np.ascontiguousarray(materials, np.float32).reshape(-1, 32)
+        self._rc(N.dev.yrtDebugShade(self.h, int(mode), obj, rows.ctypes.data, rows.shape[0],
+                                     None if m is None else m.ctypes.data, 0 if m is None else m.shape[0],
+                                     out.ctypes.data), "yrtDebugShade")
+        return out
+
     # -- rendering (device.h:223-234)
     def rtRenderFrame(self, renderer, camera, scene, toneMapper, frameBuffer, accumulate=0):
         self._rc(N.dev.yrtRenderFrame(self.h, renderer, camera, scene, toneMapper, frameBuffer, int(accumulate)),
