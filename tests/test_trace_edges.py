@@ -29,19 +29,10 @@ import pytest
 
 import oracle
 import trace_scenes as ts
+from trace_scenes import bits as _bits, compare as _compare, ids as _ids, query as _query  # noqa: F401
 
 RING = 16                # YRT_LDS_STACK*: entries of the LDS ring
 DEEP = 2 * RING + 2      # a second spilled generation, plus the kernel's parked leaf and pop-ahead
-SENT_F = np.float32(-12345.0)
-SENT_I = 0x5A5A5A5A
-
-
-def _ids(hit):
-    return np.ascontiguousarray(hit[:, 3]).view(np.int32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _references(S, org, dr):
@@ -193,37 +184,6 @@ def test_oracle_ray_along_a_box_face(exact_cpu):
 
 
 # ============================================================================= GPU
-def _query(dev, scene, org, dr, n=None, guard=64):
-    """yrtIntersect and yrtOccluded on the first n rays into sentinel-filled outputs with `guard`
-    spare elements: every slot < n written, the guard untouched. Returns (hit (n, 4), occ (n,))."""
-    import torch
-    n = len(org) if n is None else n
-    o = torch.from_numpy(np.array(org[:max(n, 1)], np.float32)).cuda()
-    d = torch.from_numpy(np.array(dr[:max(n, 1)], np.float32)).cuda()
-    hit = torch.full((n + guard, 4), float(SENT_F), dtype=torch.float32, device="cuda")
-    occ = torch.full((n + guard,), SENT_I, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
-    dev.intersect(scene, o.data_ptr(), d.data_ptr(), n, hit.data_ptr())
-    dev.occluded(scene, o.data_ptr(), d.data_ptr(), n, occ.data_ptr())
-    h, c = hit.cpu().numpy(), occ.cpu().numpy()
-    assert (h[n:] == SENT_F).all() and (c[n:] == SENT_I).all(), "guard region written"
-    assert (_ids(h[:n]) != _ids(np.full((1, 4), SENT_F))[0]).all() and (c[:n] != SENT_I).all(), "slot not written"
-    return h[:n], c[:n]
-
-
-def _compare(h, c, ref_hit, ref_occ):
-    """Triangle ids and occlusion flags bit-exact; t, u, v of hits bitwise equal (the same
-    operations without contraction and a correctly rounded division)."""
-    want = _ids(ref_hit)
-    bad = np.flatnonzero(_ids(h) != want)
-    assert len(bad) == 0, (len(bad), bad[:8], _ids(h)[bad[:8]], want[bad[:8]])
-    assert np.array_equal(c, ref_occ), np.flatnonzero(c != ref_occ)[:8]
-    m = want >= 0
-    for k, name in enumerate("tuv"):
-        d = np.flatnonzero(_bits(h[m, k]) != _bits(ref_hit[m, k]))
-        assert len(d) == 0, (name, len(d), h[m, k][d[:4]], ref_hit[m, k][d[:4]])
-
-
 @pytest.fixture(scope="module")
 def chain_gpu(gpu_device):
     S = ts.chain_scene(gpu_device)

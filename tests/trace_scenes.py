@@ -1,5 +1,5 @@
 """Scenes, rays and a brute-force reference for the ray-query kernel's edge tests
-(tests/test_trace_edges.py).
+(tests/test_trace_edges.py), and the scene, poses and rays of the refit tests (tests/test_refit.py).
 
 Everything is built through the device API (rtNewShape("trianglemesh"), positions, indices), so
 the same builders serve the host-only device of the CPU tests and the MI355X.
@@ -15,52 +15,71 @@ INF = np.float32(np.inf)
 # ----------------------------------------------------------------------------- scene building
 class MeshScene:
     """A committed scene of triangle meshes (one Matte material, optionally an ambient light) and a
-    pinhole camera. meshes: [(positions (n, 3), indices (m, 3), cullBackFaces)] in primitive-slot
-    order; global triangle ids count through the meshes in that order."""
+    pinhole camera. meshes: [(positions (n, 3), indices (m, 3), cullBackFaces[, normals (n, 3)])] in
+    primitive-slot order; global triangle ids count through the meshes in that order."""
 
     def __init__(self, dev, meshes, eye=(0, 0, -10), look=(0, 0, 0), up=(0, 1, 0), angle=60.0, light=None):
         from test_cpu_host import yrt_lookat
         d = self.dev = dev
-        mat = d.rtNewMaterial("Matte")
+        mat = self.mat = d.rtNewMaterial("Matte")
         d.rtSetFloat3(mat, "reflectance", 0.5, 0.5, 0.5)
         d.rtCommit(mat)
         self.scene = d.rtNewScene("default")
-        tri9, flags = [], []
-        for slot, (pos, idx, cull) in enumerate(meshes):
-            pos = np.ascontiguousarray(pos, F)
-            idx = np.ascontiguousarray(idx, np.int32)
-            mesh = d.rtNewShape("trianglemesh")
-            dp, di = d.rtNewData("immutable", pos), d.rtNewData("immutable", idx)
-            d.rtSetArray(mesh, "positions", "float3", dp, len(pos), 12)
-            d.rtSetArray(mesh, "indices", "int3", di, len(idx), 12)
-            if cull:
-                d.rtSetBool1(mesh, "cullBackFaces", True)
-            d.rtCommit(mesh)
-            d.rtSetPrimitive(self.scene, slot, d.rtNewShapePrimitive(mesh, mat))
-            tri9.append(pos[idx].reshape(-1, 9))
-            flags.append(np.full(len(idx), 1 if cull else 0, np.uint32))
+        self.meshes = []
+        for slot, m in enumerate(meshes):
+            pos, idx, cull = m[:3]
+            self.meshes.append({"idx": np.ascontiguousarray(idx, np.int32), "cull": bool(cull)})
+            self._set_mesh(slot, pos, m[3] if len(m) > 3 else None)
         if light is not None:
             amb = d.rtNewLight("ambientlight")
             d.rtSetFloat3(amb, "L", light, light, light)
             d.rtCommit(amb)
             d.rtSetPrimitive(self.scene, len(meshes), d.rtNewLightPrimitive(amb))
-        d.rtCommit(self.scene)
-        self.tri9 = np.concatenate(tri9).astype(F)       # (T, 9): v0 v1 v2 by global id
-        self.flags = np.concatenate(flags)                # (T,): bit 0 = cullBackFaces
         self.camera = d.rtNewCamera("pinhole")
         d.rtSetTransform(self.camera, "local2world", yrt_lookat(eye, look, up))
         d.rtSetFloat1(self.camera, "angle", angle)
         d.rtSetFloat1(self.camera, "aspectRatio", 1.0)
         d.rtCommit(self.camera)
-        self.info = d.scene_info(self.scene)
+        self.commit()
+
+    def _set_mesh(self, slot, pos, nor, mat=None):
+        """A new trianglemesh of the slot's indices and cull flag in the slot (not committed)."""
+        d, m = self.dev, self.meshes[slot]
+        m["pos"] = pos = np.ascontiguousarray(pos, F)
+        m["nor"] = nor = None if nor is None else np.ascontiguousarray(nor, F)
+        idx = m["idx"]
+        mesh = d.rtNewShape("trianglemesh")
+        d.rtSetArray(mesh, "positions", "float3", d.rtNewData("immutable", pos), len(pos), 12)
+        if nor is not None:
+            d.rtSetArray(mesh, "normals", "float3", d.rtNewData("immutable", nor), len(nor), 12)
+        d.rtSetArray(mesh, "indices", "int3", d.rtNewData("immutable", idx), len(idx), 12)
+        if m["cull"]:
+            d.rtSetBool1(mesh, "cullBackFaces", True)
+        d.rtCommit(mesh)
+        d.rtSetPrimitive(self.scene, slot, d.rtNewShapePrimitive(mesh, self.mat if mat is None else mat))
+
+    def commit(self):
+        """rtCommit of the scene; tri9, flags, info and blob follow the meshes as they are now."""
+        self.dev.rtCommit(self.scene)
+        self.tri9 = np.concatenate([m["pos"][m["idx"]].reshape(-1, 9) for m in self.meshes]).astype(F)  # v0 v1 v2 by id
+        self.flags = np.concatenate([np.full(len(m["idx"]), 1 if m["cull"] else 0, np.uint32) for m in self.meshes])
+        self.info = self.dev.scene_info(self.scene)
         self.blob = self.frame("debug")[1]
 
-    def frame(self, renderer, spp=1):
-        """(renderer handle, frame blob) of a "debug" or "pathtracer" (depth 2) renderer."""
+    def move(self, slot, positions, normals=None, commit=True):
+        """The slot's mesh with new positions (and vertex normals; None keeps the mesh's own): a
+        new trianglemesh with the same indices, material and cull flag, set into the slot, and the
+        scene committed. commit=False leaves the commit to a later move or commit()."""
+        self._set_mesh(slot, positions, self.meshes[slot]["nor"] if normals is None else normals)
+        if commit:
+            self.commit()
+
+    def frame(self, renderer, spp=1, depth=2):
+        """(renderer handle, frame blob) of a "debug" or "pathtracer" (maxDepth depth) renderer."""
         d = self.dev
         r = d.rtNewRenderer(renderer)
         if renderer == "pathtracer":
-            d.rtSetInt1(r, "maxDepth", 2)
+            d.rtSetInt1(r, "maxDepth", depth)
             d.rtSetFloat1(r, "tMaxShadowRay", 1e4)
         d.rtSetInt1(r, "sampler.spp", spp)
         d.rtCommit(r)
@@ -453,3 +472,188 @@ def node_plane_rays(qnodes, lo, hi):
                         org.append([xy[0], xy[1], 0.0, 0.0]); dr.append([sx, sy, 1.0, np.inf])
                         org.append([xy[0], xy[1], 2.0, 0.0]); dr.append([sx, sy, -1.0, np.inf])
     return np.array(org, F).reshape(-1, 4), np.array(dr, F).reshape(-1, 4)
+
+
+# ----------------------------------------------------------------------------- ray queries on the device
+SENT_F = np.float32(-12345.0)
+SENT_I = 0x5A5A5A5A
+
+
+def ids(hit):
+    return np.ascontiguousarray(hit[:, 3]).view(np.int32)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def query(dev, scene, org, dr, n=None, guard=64):
+    """yrtIntersect and yrtOccluded on the first n rays into sentinel-filled outputs with `guard`
+    spare elements: every slot < n written, the guard untouched. Returns (hit (n, 4), occ (n,))."""
+    import torch
+    n = len(org) if n is None else n
+    o = torch.from_numpy(np.array(org[:max(n, 1)], np.float32)).cuda()
+    d = torch.from_numpy(np.array(dr[:max(n, 1)], np.float32)).cuda()
+    hit = torch.full((n + guard, 4), float(SENT_F), dtype=torch.float32, device="cuda")
+    occ = torch.full((n + guard,), SENT_I, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    dev.intersect(scene, o.data_ptr(), d.data_ptr(), n, hit.data_ptr())
+    dev.occluded(scene, o.data_ptr(), d.data_ptr(), n, occ.data_ptr())
+    h, c = hit.cpu().numpy(), occ.cpu().numpy()
+    assert (h[n:] == SENT_F).all() and (c[n:] == SENT_I).all(), "guard region written"
+    assert (ids(h[:n]) != ids(np.full((1, 4), SENT_F))[0]).all() and (c[:n] != SENT_I).all(), "slot not written"
+    return h[:n], c[:n]
+
+
+def compare(h, c, ref_hit, ref_occ):
+    """Triangle ids and occlusion flags bit-exact; t, u, v of hits bitwise equal (the same
+    operations without contraction and a correctly rounded division)."""
+    want = ids(ref_hit)
+    bad = np.flatnonzero(ids(h) != want)
+    assert len(bad) == 0, (len(bad), bad[:8], ids(h)[bad[:8]], want[bad[:8]])
+    assert np.array_equal(c, ref_occ), np.flatnonzero(c != ref_occ)[:8]
+    m = want >= 0
+    for k, name in enumerate("tuv"):
+        d = np.flatnonzero(bits(h[m, k]) != bits(ref_hit[m, k]))
+        assert len(d) == 0, (name, len(d), h[m, k][d[:4]], ref_hit[m, k][d[:4]])
+
+
+# ----------------------------------------------------------------------------- refit scene
+# primitive slots of refit_meshes()
+R_GRID, R_GRID2, R_QUAD, R_SLIVERS, R_ZERO, R_FAR, R_TINY, R_POINT = range(8)
+REFIT_SCALE = 16.0  # of the grids, the quad and the slivers: child boxes overlap by more than the spatial
+#                     splits' threshold, 1e-5 of the root box's area, which R_FAR makes large
+REFIT_EYE, REFIT_LOOK = (264.0, 1312.0, -964.0), (264.0, 912.0, -564.0)  # on the first grid under refit_pose_a
+
+
+def height_field(nx, nz, at, rng, normals=False):
+    """nx x nz quads (two triangles each) over a jittered unit grid in x and z from `at`, with
+    random heights in [0, 1.5]; normals: unit vertex normals tilted at random off +y."""
+    x, z = np.meshgrid(np.arange(nx + 1.0), np.arange(nz + 1.0))
+    n = x.size
+    pos = np.stack([x.ravel() + rng.uniform(-0.3, 0.3, n), rng.uniform(0.0, 1.5, n),
+                    z.ravel() + rng.uniform(-0.3, 0.3, n)], 1) + np.asarray(at, np.float64)
+    tri = []
+    for j in range(nz):
+        for i in range(nx):
+            a, b, c, d = j * (nx + 1) + i, j * (nx + 1) + i + 1, (j + 1) * (nx + 1) + i + 1, (j + 1) * (nx + 1) + i
+            tri += [[a, b, c], [a, c, d]]
+    nor = None
+    if normals:
+        nor = np.stack([rng.uniform(-0.4, 0.4, n), np.ones(n), rng.uniform(-0.4, 0.4, n)], 1)
+        nor = (nor / np.linalg.norm(nor, axis=1, keepdims=True)).astype(F)
+    return pos.astype(F) + F(0), np.array(tri, np.int32), nor
+
+
+def refit_meshes(seed=23):
+    """The refit tests' scene, in slot order (fixed seed; no coordinate is -0.0, so a minimum is
+    the same bits in whatever order it is taken; sizes before REFIT_SCALE, which applies to the
+    first four):
+      R_GRID: a 23 x 17 height field (782 triangles, not a multiple of 64) with vertex normals;
+      R_GRID2: a 9 x 31 height field (558 triangles); R_QUAD: one quad;
+      R_SLIVERS: 40 triangles 25 long and 0.02 wide across both grids, cullBackFaces;
+      R_ZERO: 5 triangles of all-zero vertices; R_FAR: a 2 x 2 field at x = 1e6;
+      R_TINY: a 2 x 2 field scaled by 1e-30; R_POINT: a triangle collapsed to a point beside one
+      of negative coordinates."""
+    rng = np.random.default_rng(seed)
+    g0, i0, n0 = height_field(23, 17, (0, 0, 0), rng, normals=True)
+    g1, i1, _ = height_field(9, 31, (30, 0, -6), rng)
+    q, iq, _ = height_field(1, 1, (-5, 1, 2), rng)
+    a = rng.uniform([0, 0, 0], [40, 2, 18], size=(40, 3))
+    u = rng.normal(size=(40, 3)) * [1, 0.1, 1]
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    w = np.cross(u, [0, 1, 0])
+    w /= np.linalg.norm(w, axis=1, keepdims=True)
+    sl = np.stack([a, a + 25.0 * u, a + 0.02 * w], 1).reshape(-1, 3).astype(F) + F(0)
+    isl = np.arange(120, dtype=np.int32).reshape(40, 3)
+    g0, g1, q, sl = (p * F(REFIT_SCALE) for p in (g0, g1, q, sl))
+    far, ifar, _ = height_field(2, 2, (1e6, 0, 0), rng)
+    tiny, itiny, _ = height_field(2, 2, (1, 1, 1), rng)
+    tiny = tiny * F(1e-30)
+    pt = np.array([[3, -2, 4]] * 3 + [[-7, -3, -2], [-6, -3, -2], [-7, -2, -3]], F)
+    ipt = np.array([[0, 1, 2], [3, 4, 5]], np.int32)
+    meshes = [(g0, i0, False, n0), (g1, i1, False), (q, iq, False), (sl, isl, True),
+              (np.zeros((15, 3), F), np.arange(15, dtype=np.int32).reshape(5, 3), False),
+              (far, ifar, False), (tiny, itiny, False), (pt, ipt, False)]
+    for m in meshes:
+        assert not np.signbit(m[0][m[0] == 0]).any()
+    return meshes
+
+
+def refit_scene(dev):
+    """refit_meshes() under an ambient light; the camera looks at where refit_pose_a puts R_GRID."""
+    return MeshScene(dev, refit_meshes(), eye=REFIT_EYE, look=REFIT_LOOK, light=2.0)
+
+
+def _turn(pos, nor, axis, angle, shift):
+    """pos turned about its centroid (Rodrigues' formula) and shifted, nor turned with it."""
+    k = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    R = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
+    p = np.asarray(pos, np.float64)
+    c = p.mean(0)
+    out = ((p - c) @ R.T + c + np.asarray(shift, np.float64)).astype(F) + F(0)
+    return out, None if nor is None else (np.asarray(nor, np.float64) @ R.T).astype(F) + F(0)
+
+
+def refit_pose_a(S):
+    """(a): R_GRID turned by 0.7 rad about (1, 2, 3) and shifted by 900 in y and -700 in z, out of
+    the built scene's bounds."""
+    m = S.meshes[R_GRID]
+    S.move(R_GRID, *_turn(m["pos"], m["nor"], (1, 2, 3), 0.7, (80, 900, -700)))
+
+
+def refit_pose_b(S):
+    """(b): the quad, the slivers and the second grid moved in one commit."""
+    S.move(R_QUAD, _turn(S.meshes[R_QUAD]["pos"], None, (0, 0, 1), 2.0, (140, -25, 50))[0], commit=False)
+    S.move(R_SLIVERS, _turn(S.meshes[R_SLIVERS]["pos"], None, (0, 1, 0), 0.5, (0, 60, 0))[0], commit=False)
+    S.move(R_GRID2, S.meshes[R_GRID2]["pos"] + F([8.5, -50, 4.25]))
+
+
+def refit_pose_c(S):
+    """(c): the second grid collapsed to one point."""
+    S.move(R_GRID2, np.tile(F([504.5, 36.25, 114.125]), (len(S.meshes[R_GRID2]["pos"]), 1)))
+
+
+def refit_pose_d(S):
+    """(d): R_GRID carried to coordinates near -3e5 (float spacing there: 1/32)."""
+    S.move(R_GRID, S.meshes[R_GRID]["pos"] + F([-3e5, -3e5, -3e5]))
+
+
+REFIT_POSES = (refit_pose_a, refit_pose_b, refit_pose_c, refit_pose_d)
+
+
+def refit_rays(S, old9, new9, n, seed=17):
+    """Rays for a scene S in which one mesh moved (old9 -> new9, its triangles before and after),
+    interleaved by index % 3: 0: aimed at a triangle of new9, 1: at one of old9 (from 160 to 480
+    away, the aim jittered by 3), 2: from a point inside the scene's bounds as they are now, short
+    of R_FAR (whose 1e6 would leave the rest a speck in the box), in a random direction or, every
+    second one, towards a vertex of the scene. Returns (org4, dir4 with tfar inf, dir4 with half of the rays
+    cut at a finite tfar: 0.5 to 1.5 times the distance to the aim, 300 for kind 2)."""
+    rng = np.random.default_rng(seed)
+    org = np.zeros((n, 4), F)
+    dr = np.zeros((n, 4), F)
+    dr[:, 3] = INF
+    far = np.full(n, 300.0)
+    kind = np.arange(n) % 3
+    for k, t9 in ((0, new9), (1, old9)):
+        m = np.flatnonzero(kind == k)
+        cen = np.asarray(t9, np.float64).reshape(-1, 3, 3).mean(1)
+        aim = cen[rng.integers(0, len(cen), len(m))] + rng.uniform(-3, 3, (len(m), 3))
+        v = rng.normal(size=(len(m), 3))
+        v /= np.linalg.norm(v, axis=1, keepdims=True)
+        dist = rng.uniform(160, 480, len(m))
+        org[m, :3] = aim + v * dist[:, None]
+        dr[m, :3] = -v
+        far[m] = dist * rng.uniform(0.5, 1.5, len(m))
+    m = np.flatnonzero(kind == 2)
+    v9 = np.concatenate([m["pos"] for k, m in enumerate(S.meshes) if k != R_FAR]).astype(np.float64)
+    org[m, :3] = rng.uniform(v9.min(0), v9.max(0), (len(m), 3))
+    v = rng.normal(size=(len(m), 3))
+    aimed = np.arange(len(m)) % 2 == 1                   # every second one towards some vertex, not quite at it
+    v[aimed] = v9[rng.integers(0, len(v9), int(aimed.sum()))] + rng.uniform(-3, 3, (int(aimed.sum()), 3)) - org[m[aimed], :3]
+    dr[m, :3] = v / np.linalg.norm(v, axis=1, keepdims=True)
+    cut = dr.copy()
+    half = (np.arange(n) // 3) % 2 == 0
+    cut[half, 3] = far[half]
+    return org, dr, cut

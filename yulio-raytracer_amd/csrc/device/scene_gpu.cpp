@@ -564,6 +564,19 @@ bool refit_gpu_scene(GpuScene& S, const std::vector<std::shared_ptr<ScenePrim>>&
     launch_refit_nodes(S.nodes.as<GpuNode>(), S.tris.as<GpuTri>(), S.indices.as<int4>(), S.positions.as<float4>(),
                        S.levelNodes.as<int>() + S.levelStart[d], S.levelStart[d + 1] - S.levelStart[d], stream);
   launch_quantize_nodes(S.nodes.as<GpuNode>(), S.qnodes.as<GpuQNode>(), (int)S.hNodes.size(), stream);
+  // the scene bounds, as the build takes them: over the vertices the triangles reference
+  for (int k = 0; k < 3; ++k) { S.bboxLo[k] = INFINITY; S.bboxHi[k] = -INFINITY; }
+  for (const auto& p : prims) {
+    if (!p || !p->shape) continue;
+    const MeshInst& m = *p->shape;
+    for (int v : m.tri) {
+      const float c[3] = {m.pos[v].x, m.pos[v].y, m.pos[v].z};
+      for (int k = 0; k < 3; ++k) {
+        S.bboxLo[k] = std::min(S.bboxLo[k], c[k]);
+        S.bboxHi[k] = std::max(S.bboxHi[k], c[k]);
+      }
+    }
+  }
   HIP_CHECK(hipStreamSynchronize(stream));
   S.hostBvhStale = true;
   S.refits++;
