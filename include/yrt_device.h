@@ -351,6 +351,13 @@ YRT_API int yrtDebugShade(YRTDevice dev, int mode, YRTHandle object, const float
  * (common/yrt_tile_scatter.h: a fixed bijection of [0, T), used by the renderer and the gather
  * whenever the tile stride is above 1). Host-side; -1 for t outside [0, T). */
 YRT_API int yrtDebugTileScatter(int t, int T);
+/* The batch plan of a wavefront job over shardTiles tiles at spp samples per pixel: how a
+ * device with `lanes` lanes and a batch capacity of `capacity` paths (yrtSetBatchCapacity)
+ * cuts the job into batches. capture != 0: a ray-capture frame (yrtSetRayCapture); grow: the
+ * YRT_BATCH_GROW switch. out4 = tiles per batch, batches, paths per batch, lanes used.
+ * Host-side (the plan changes speed only, never pixels); -1 on an argument out of range. */
+YRT_API int yrtDebugBatchPlan(int64_t shardTiles, int spp, int64_t capacity, int lanes, int capture, int grow,
+                              int64_t* out4);
 /* Parity debugging: out4 == NULL arms the capture of the per-sample radiance (the pathL terms
  * the resolve sums, in s order) of pixel id y*width+x (-1 disarms) of frame `frame` for the
  * following renders (buffer of maxSamples float4); out4 != NULL copies the captured samples

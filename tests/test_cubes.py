@@ -97,7 +97,7 @@ def test_cube_job_shards_compose(gpu_device):
 @pytest.mark.parametrize("n", [8, 4])
 def test_batch_grow_invariance(gpu_device, monkeypatch, n):
     """A rank's share of the full-size C4 cube job runs 7 (N = 8) or 14 (N = 4) batches per lane
-    at the default capacity, so Device::render_shard grows them to 2x / 1.5x the size; the faces
+    at the default capacity, so plan_batches grows them to 2x / 1.5x the size; the faces
     are bit-identical to the share rendered without growing (YRT_BATCH_GROW=0)."""
     s = yrt.Session(c4_args() + ["-fb", "RGB8"], device=gpu_device)
     faces = []

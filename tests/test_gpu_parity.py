@@ -294,7 +294,7 @@ def test_tile_shards_compose_bit_exact(gpu_device):
             gpu_device.set_tile_shard(k, 3)
             parts.append(s.render())
             # the same shard again: its frame block already holds the zeros outside the shard
-            # and is not cleared again (device.cpp FrameBlock::zeroKey)
+            # and is not cleared again (render.cpp FrameBlock::zeroKey)
             assert np.array_equal(s.render(), parts[-1])
         gpu_device.set_tile_shard(0, 1)
         assert np.array_equal(s.render(), full)
@@ -314,7 +314,7 @@ def test_multi_device_tile_shards_compose_bit_exact(gpu_device):
     """A process of two logical devices (devices=0,0) rendering a process-level shard
     (yrtSetTileShard(k, 3), no communicator): the pixels of the other processes' shards read as
     zeros in every render, including a fresh frame block and one that held a whole frame, so the
-    three per-process images sum to the one-device frame (device.cpp shard clear)."""
+    three per-process images sum to the one-device frame (render.cpp shard clear)."""
     from yrt.dist import tile_mask
     args = c2_args(200, 4) + ["-fb", "RGB_FLOAT32"]
     s = yrt.Session(args, device=gpu_device)

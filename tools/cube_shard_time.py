@@ -114,7 +114,7 @@ def main():
             if n > 1:
                 # untimed: a rank of an N-GPU run renders the same share every frame, so its
                 # two frame blocks (render k+1 writes the block render k's unread frames do
-                # not hold) already hold zeros outside the share (device.cpp FrameBlock::zeroKey)
+                # not hold) already hold zeros outside the share (render.cpp FrameBlock::zeroKey)
                 for _ in range(2):
                     render_cube(ses, a.cfg, a.mode)
             reps = []

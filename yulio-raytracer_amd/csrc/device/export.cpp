@@ -93,11 +93,6 @@ struct BlobWriter {
 
 using namespace yrt;
 
-struct YRTDevice_;
-namespace yrt {
-// defined in device.cpp
-}
-
 extern "C" int64_t yrt_export_frame_impl(const Object* renderer, const Object* camera, const SceneObj* scene,
                                          uint32_t frameSeed, void* buf, size_t bytes) {
   BlobWriter w;

@@ -160,7 +160,7 @@ struct SceneObj : Object {
   std::vector<std::shared_ptr<ScenePrim>> slots;
   std::shared_ptr<GpuScene> gpu;
   // copies of `gpu` on the other HIP devices of a multi-GPU device (by HIP device id),
-  // re-made when the scene is rebuilt or refit (device.cpp scene_on)
+  // re-made when the scene is rebuilt or refit (Device::scene_on, device.cpp)
   std::map<int, std::shared_ptr<GpuScene>> replicas;
   explicit SceneObj(const std::string& t) : Object(Kind::SCENE, t) {}
   void commit() override;
@@ -231,7 +231,7 @@ struct FrameBufferObj : Object {
   std::vector<void*> userPtrs;
   std::vector<float> accu;                 // AccuBuffer (x,y,z,w) per pixel
   // A frame still on the device (per buffer id): rtRenderFrame leaves it in HBM and
-  // rtMapFrameBuffer copies it to the host pixels on first access (device.cpp fb_read_back).
+  // rtMapFrameBuffer copies it to the host pixels on first access (fb_read_back, device.cpp).
   struct Pending {
     std::shared_ptr<void> keep;  // the device block holding the frame (kept alive until read)
     const void* src = nullptr;   // RGB8 rows (RGB8 framebuffers) or RGB float32 (the others)

@@ -190,7 +190,7 @@ int check_math_table(int fn, const uint16_t* table2048, unsigned long long* host
 // host pointers; mats numMats records (may be null), cam / light one host record for modes 2 / 3
 int check_shade(int mode, int n, const float* rows, const GpuMaterial* mats, int numMats, const GpuCamera* cam,
                 const GpuLight* light, float* out);
-// Multi-GPU gather (device.cpp): the pixels of the tiles of one shard (job tile =
+// Multi-GPU gather (device/gather_device.cpp): the pixels of the tiles of one shard (job tile =
 // tileOffset + j * tileStride, j < numTiles, over numFrames stacked frames of tilesPerFrame
 // tiles) as a slab of numTiles * 256 elements in tile order j and scan order within the tile;
 // unpack scatters a slab back into the frames. Elements are 32-bit RGB8 words (rgb8 = 1: the

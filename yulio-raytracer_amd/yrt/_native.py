@@ -185,6 +185,10 @@ try:  # round 6; absent from older tuning builds selected with YRT_LIB_DIR
     _sig(dev, "yrtDebugTileScatter", i32, i32, i32)
 except AttributeError:
     pass
+try:  # absent from older builds selected with YRT_LIB_DIR
+    _sig(dev, "yrtDebugBatchPlan", i32, C.c_int64, i32, C.c_int64, i32, i32, i32, C.POINTER(C.c_int64))
+except AttributeError:
+    pass
 try:  # the shading-layer probe; absent from older builds selected with YRT_LIB_DIR
     _sig(dev, "yrtDebugShade", i32, vp, i32, vp, vp, i32, vp, i32, vp)
 except AttributeError:
