@@ -336,7 +336,7 @@ YRT_API int yrtDebugCheckMath(YRTDevice dev, int fn, uint64_t* out2);
  * reconstruction from table2048 (the 12-bit mantissas of tests/golden/sse_rcp_tables.json) for
  * all 2^32 inputs. out2 as yrtDebugCheckMath. */
 YRT_API int yrtDebugCheckMathTable(YRTDevice dev, int fn, const uint16_t* table2048, uint64_t* out2);
-/* Test-only probe of the device's shading layer (k_check_shade, kernels/k_aux.h): runs the
+/* Test-only probe of the device's shading layer (k_check_shade, kernels/k_checks.h): runs the
  * kernels' own BRDF component, CompositedBRDF, camera and light functions on n rows, so that
  * tests can compare them with the reference's classes bit for bit. rows: n x 48 words (wo, Ns, Ng,
  * Tx, Ty, wi, s.xy, ss, component count, 2 pad, 3 x (kind, R.rgb, a, b, c, pad)); out: n x 12

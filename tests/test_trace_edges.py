@@ -20,9 +20,11 @@ u and v: the oracle divides U / |den| and V / |den| like the kernel, and brute f
 the simulation agree on t, u, v bit for bit on every scene. On the MI355X t, u and v of every
 hit in every test below were bitwise equal to them as well; no tolerance is used.
 
-Finding: the brute force disagreed with the oracle (and the float-node box test of k_pick /
-k_debug shared the flaw) for rays along a box face, see test_oracle_ray_along_a_box_face and
-test_pick_along_a_box_face; both box tests were fixed.
+Finding: the brute force disagreed with the oracle (and the float-node box test that k_pick /
+k_debug had then shared the flaw) for rays along a box face, see test_oracle_ray_along_a_box_face
+and test_pick_along_a_box_face; both box tests were fixed. The device has since dropped that box
+test: k_pick, k_debug and k_guides walk the quantized nodes through closest_hit, with k_trace's
+box test, and test_guides_equal_ray_queries compares the two kernels directly.
 """
 import numpy as np
 import pytest
@@ -208,7 +210,7 @@ def test_chain_queries_gpu(gpu_device, chain_gpu):
 
 @pytest.mark.gpu
 def test_chain_debug_frame_and_pick(gpu_device, chain_gpu):
-    """The same scene through traverse<> (float nodes, private 64-entry stack): a 64 x 64 debug
+    """The same scene through closest_hit (quantized nodes, private 64-entry stack): a 64 x 64 debug
     frame is bit-exact against the oracle, and a pick along the axis returns the brute-force hit
     point on the backstop."""
     S = chain_gpu
@@ -334,8 +336,9 @@ def test_exact_cases_gpu(gpu_device):
 
 @pytest.mark.gpu
 def test_pick_along_a_box_face(gpu_device):
-    """traverse<> on the float nodes, whose planes are the triangles' own coordinates: the exact
-    scene's camera looks up the z axis from (4, 2, -10), along the face x = 4 of the copies' box.
+    """closest_hit on a ray along a box face (float-node planes are the triangles' own coordinates,
+    the quantized nodes' lie a quantum outside): the exact scene's camera looks up the z axis from
+    (4, 2, -10), along the face x = 4 of the copies' box.
     The pick finds the quad's edge at (4, 2, 1), and the debug frame equals the oracle's."""
     S = ts.exact_scene(gpu_device)
     r, blob = S.frame("debug")
@@ -349,3 +352,31 @@ def test_pick_along_a_box_face(gpu_device):
     img = S.render(r, 64)
     ref, _ = oracle.render(blob, 64, 64, 1.0)
     assert np.array_equal(img, ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["chain", "exact"])
+def test_guides_equal_ray_queries(gpu_device, chain_gpu, which):
+    """One closest-hit rule on the device: the guide pass (k_guides, closest_hit with its private
+    stack) and the ray-query kernel (yrtIntersect, k_trace) answer the same 64 x 64 pixel-centre
+    camera rays alike: the guides' hit mask (pos4.w < inf) is the query's tri >= 0, and pos4.w
+    is the query's t bit for bit on every hit; both equal brute force. The rays are the oracle's
+    camera rays through ((x + .5) / 64, (y + .5) / 64), the kernel's own (exact quotients). On the
+    chain every one of them reaches stack height >= 34 (test_chain_camera_rays_are_deep), where
+    k_trace spills."""
+    S = chain_gpu if which == "chain" else ts.exact_scene(gpu_device)
+    pos, _ = gpu_device.render_guides(S.camera, S.scene, 64, 64)
+    gt = np.ascontiguousarray(pos[..., 3], np.float32).reshape(-1)
+    px = (np.stack(np.meshgrid(np.arange(64), np.arange(64)), -1).reshape(-1, 2) + 0.5) / 64.0
+    o, d = oracle.camera_rays(S.blob, px)
+    org = np.concatenate([o, np.zeros((len(o), 1), np.float32)], 1)
+    dr = np.concatenate([d, np.full((len(d), 1), np.inf, np.float32)], 1)
+    h, _ = _query(gpu_device, S.scene, org, dr)
+    bh, _ = ts.brute_force(S.tri9, S.flags, org, dr)
+    hit = gt < np.inf
+    print(which, "guide hits:", int(hit.sum()), "of", len(gt))
+    assert 0 < hit.sum()
+    for name, ref in (("yrtIntersect", h), ("brute force", bh)):
+        assert np.array_equal(hit, _ids(ref) >= 0), (name, np.flatnonzero(hit != (_ids(ref) >= 0))[:8])
+        bad = np.flatnonzero(_bits(gt[hit]) != _bits(ref[hit, 0]))
+        assert len(bad) == 0, (name, len(bad), gt[hit][bad[:4]], ref[hit, 0][bad[:4]])

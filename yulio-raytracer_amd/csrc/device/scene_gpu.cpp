@@ -19,7 +19,6 @@ namespace yrt {
 // SceneView pointers of the scene's own device buffers (counts already set in S.view)
 static void bind_view(GpuScene& S) {
   SceneView& v = S.view;
-  v.nodes = S.nodes.as<GpuNode>();
   v.qnodes = S.qnodes.as<GpuQNode>();
   v.tris = S.tris.as<GpuTri>();
   v.triGeom = S.triGeom.as<int>();

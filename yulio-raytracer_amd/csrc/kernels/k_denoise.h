@@ -1,0 +1,123 @@
+// k_denoise.h — the denoiser's filter: the framebuffer load (with demodulation) and the
+// edge-avoiding à-trous iterations; its guide frames come from k_guides (k_firsthit.h).
+#pragma once
+
+#include "yrt_kernels.h"
+#include "yrt_wave.h"
+#include "../common/yrt_libm.h"
+
+namespace yrt {
+
+// A framebuffer as the filter reads and writes it: float or 8-bit channels, 3 or 4 per pixel,
+// rows rowStride channels apart (RGB8 rows are padded to 4 bytes).
+__device__ __forceinline__ size_t fb_channel(const FrameIO& io, int x, int y) {
+  return (size_t)y * io.rowStride + (size_t)x * io.pixStride;
+}
+
+// c_0 of the filter: the framebuffer's pixels as float4 (8-bit channels as byte / 255).
+// DEMOD (YRTDenoiseParams::demodulate): a hit pixel's modulation m = max(albedo, floor) ^ power
+// per channel goes to mod4 and the filter's input is d_0 = c_0 / m (IEEE divisions); a miss
+// pixel, which the filter neither reads nor writes, keeps c_0 and gets m = 1.
+template <bool DEMOD>
+__global__ __launch_bounds__(YRT_BLOCK) void k_atrous_load(FrameIO io, float4* __restrict__ dst,
+                                                           const float4* __restrict__ albedo4, float albedoFloor,
+                                                           float albedoPower, float4* __restrict__ mod4) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)io.width * io.height) return;
+  const int y = (int)(i / io.width), x = (int)(i - (long long)y * io.width);
+  const size_t o = fb_channel(io, x, y);
+  float4 c;
+  if (io.bytes) {
+    const uint8_t* p = (const uint8_t*)io.pixels + o;
+    c = make_float4(float(p[0]) / 255.0f, float(p[1]) / 255.0f, float(p[2]) / 255.0f, 0.f);
+  } else {
+    const float* p = (const float*)io.pixels + o;
+    c = make_float4(p[0], p[1], p[2], 0.f);
+  }
+  if constexpr (DEMOD) {
+    const float4 a = albedo4[i];
+    float4 m = make_float4(1.f, 1.f, 1.f, 0.f);
+    if (a.w != 0.f) {
+      m.x = yrt_powf(fmaxf(a.x, albedoFloor), albedoPower);
+      m.y = yrt_powf(fmaxf(a.y, albedoFloor), albedoPower);
+      m.z = yrt_powf(fmaxf(a.z, albedoFloor), albedoPower);
+      c = make_float4(c.x / m.x, c.y / m.y, c.z / m.z, 0.f);
+    }
+    mod4[i] = m;
+  }
+  dst[i] = c;
+}
+
+__device__ __forceinline__ float atrous_h(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
+
+// One iteration of the edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) with
+// SVGF's normal and plane-distance weights: 5x5 taps `step` pixels apart, the
+// B3-spline kernel h = (1/16, 1/4, 3/8, 1/4, 1/16) per axis, times
+//   w_n = max(0, n_p . n_q) ^ sigmaNormal
+//   w_x = exp(-|n_p . (x_q - x_p)| / (sigmaPosition t_p))
+//   w_c = exp(-|c_p - c_q|^2 / sigmaColor_i^2)                  (rcpSigmaColor2 = 0: off)
+// Taps outside the image or on a miss are skipped; the centre tap weighs h(0)^2 exactly. The
+// mean is taken as c_p + sum w (c_q - c_p) / sum w, so a constant frame stays what it is.
+// A miss pixel is not written. The last iteration (out != null) stores into the framebuffer:
+// floats as they are, bytes as k_resolve_pixels quantizes them; alpha and row padding are
+// not touched. DEMOD: the frames hold the demodulated signal d (k_atrous_load), every weight
+// acts on d, and the last iteration stores d_n m with the modulation of mod4.
+template <bool DEMOD>
+__global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const float4* __restrict__ pos4,
+                                                      const float4* __restrict__ nrm4, const float4* __restrict__ src,
+                                                      float4* __restrict__ dst, FrameIO out,
+                                                      const float4* __restrict__ mod4) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)ap.width * ap.height) return;
+  const float INF = __int_as_float(0x7f800000);
+  const float4 pp = pos4[i];
+  if (!(pp.w < INF)) return;
+  const int y = (int)(i / ap.width), x = (int)(i - (long long)y * ap.width);
+  const float4 n4 = nrm4[i], c4 = src[i];
+  const V3 xp = v3(pp.x, pp.y, pp.z), np = v3(n4.x, n4.y, n4.z), cp = v3(c4.x, c4.y, c4.z);
+  const float rcpPlane = 1.0f / (ap.sigmaPosition * pp.w);
+  V3 sum = v3s(0.f);
+  float wsum = atrous_h(0) * atrous_h(0);
+  for (int dy = -2; dy <= 2; ++dy) {
+    const long long qy = (long long)y + (long long)dy * ap.step;
+    if (qy < 0 || qy >= ap.height) continue;
+    for (int dx = -2; dx <= 2; ++dx) {
+      const long long qx = (long long)x + (long long)dx * ap.step;
+      if (qx < 0 || qx >= ap.width || (dx == 0 && dy == 0)) continue;
+      const size_t j = (size_t)qy * ap.width + (size_t)qx;
+      const float4 pq = pos4[j];
+      if (!(pq.w < INF)) continue;
+      const float4 nq = nrm4[j], cq4 = src[j];
+      const V3 d = v3(cq4.x, cq4.y, cq4.z) - cp;
+      float w = atrous_h(dx) * atrous_h(dy);
+      w = w * yrt_powf(fmaxf(0.f, dot(np, v3(nq.x, nq.y, nq.z))), ap.sigmaNormal);
+      w = w * yrt_expf(-fabsf(dot(np, v3(pq.x, pq.y, pq.z) - xp)) * rcpPlane);
+      if (ap.rcpSigmaColor2 > 0.f) w = w * yrt_expf(-dot(d, d) * ap.rcpSigmaColor2);
+      sum = sum + w * d;
+      wsum = wsum + w;
+    }
+  }
+  V3 c = cp + sum * (1.0f / wsum);
+  if (!out.pixels) {
+    dst[i] = make_float4(c.x, c.y, c.z, 0.f);
+    return;
+  }
+  if constexpr (DEMOD) {
+    const float4 m = mod4[i];
+    c = c * v3(m.x, m.y, m.z);
+  }
+  const size_t o = fb_channel(out, x, y);
+  if (out.bytes) {
+    uint8_t* p = (uint8_t*)out.pixels + o;
+    p[0] = (uint8_t)clampf(c.x * 255.0f, 0.0f, 255.0f);
+    p[1] = (uint8_t)clampf(c.y * 255.0f, 0.0f, 255.0f);
+    p[2] = (uint8_t)clampf(c.z * 255.0f, 0.0f, 255.0f);
+  } else {
+    float* p = (float*)out.pixels + o;
+    p[0] = c.x;
+    p[1] = c.y;
+    p[2] = c.z;
+  }
+}
+
+}  // namespace yrt

@@ -12,7 +12,7 @@ namespace yrt {
 // one leaf per iteration, and whenever at least YRT_REFILL lanes of the wave have finished
 // their ray, those lanes take the next rays of the chunk (ballot + popcount, no atomics).
 // This keeps 64-wide waves busy although ray costs differ by 10-100x. Same visit order and
-// the same (t, triangle id) closest-hit rule as traverse<>.
+// the same (t, triangle id) closest-hit rule as closest_hit (yrt_traverse.h).
 #ifndef YRT_REFILL
 #define YRT_REFILL 40  // 24/6 +1.3 % over 16/4; with 64-lane blocks 28/6 +0.4 %, then 40/8 +0.9 % over 28/6;
                         // with four lanes 48 everywhere: C4 -0.8 %, C3 +0.2 %, C5 +1.6 % (r05cc/dd/ee)
@@ -451,7 +451,9 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu
             // range test against the current closest hit; on a tie (t == best.t) the smaller
             // triangle id wins
             // a tie with an accepted hit (best.tri >= 0, so best.t < tfar) passes the range test
-            // by itself: one predicate instead of a re-test against tfar (C3 -0.35 %, C5 -0.3 %)
+            // by itself: one predicate instead of a re-test against tfar (C3 -0.35 %, C5 -0.3 %).
+            // The same rule as closest_hit (yrt_traverse.h), inline here: a shared helper
+            // re-allocates this kernel's registers.
             const bool tie = (t == best.t) & (best.tri >= 0) & (gid < best.tri);
             const bool ok = g & (t > r.tnear) & ((t < best.t + 0.0f) | tie);
             if (ok & (k < lTake)) {

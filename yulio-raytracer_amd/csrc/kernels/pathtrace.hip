@@ -28,7 +28,11 @@
 #include "k_trace.h"
 #include "yrt_surface.h"
 #include "k_shade.h"
-#include "k_aux.h"
+#include "k_firsthit.h"
+#include "k_denoise.h"
+#include "k_tiles.h"
+#include "k_checks.h"
+#include "k_refit.h"
 
 namespace yrt {
 

@@ -12,8 +12,9 @@
 namespace yrt {
 
 struct SceneView {
-  const GpuNode* nodes;
-  const GpuQNode* qnodes;  // the same tree, 64-B quantized nodes (k_trace)
+  const void* reserved = nullptr;  // unused (no kernel reads the float nodes): keeps the kernel-argument
+                                   // offsets of everything below, as PathBuffers::reserved does
+  const GpuQNode* qnodes;  // the tree every kernel traverses: 64-B quantized nodes (yrt_traverse.h)
   const GpuTri* tris;
   const int* triGeom;
   const int4* indices;
@@ -183,10 +184,10 @@ int trace_profile(unsigned long long* out8, int reset);
 // Debug capture: per-sample radiance of pixel id (y * width + x) of frame `frame` written to
 // out[s] by the next resolves (pixelId -1: off)
 int debug_pixel_capture(int pixelId, int frame, float4* out, int capacity);
-// Arithmetic self-check of the correctly rounded fast reciprocal (rcp_rn): see k_aux.h
+// Arithmetic self-check of the correctly rounded fast reciprocal (rcp_rn): see k_checks.h
 int check_math(int fn, unsigned long long* host2);
 int check_math_table(int fn, const uint16_t* table2048, unsigned long long* host2);
-// Shading-layer probe (k_check_shade, k_aux.h; test-only): n rows of 48 words in, 12 words out,
+// Shading-layer probe (k_check_shade, k_checks.h; test-only): n rows of 48 words in, 12 words out,
 // host pointers; mats numMats records (may be null), cam / light one host record for modes 2 / 3
 int check_shade(int mode, int n, const float* rows, const GpuMaterial* mats, int numMats, const GpuCamera* cam,
                 const GpuLight* light, float* out);
@@ -206,7 +207,7 @@ void launch_pack_tiles(const float* fbFloat, const uint8_t* fbRGB8, const SlabLa
 void launch_unpack_tiles(const void* slab, float* fbFloat, uint8_t* fbRGB8, const SlabLayout& L, int numTiles,
                          hipStream_t s);
 void launch_pick(const SceneView& sv, const GpuCamera* cam, float x, float y, float4* out, hipStream_t s);
-// Denoise (yrtRenderGuides / yrtRenderAlbedo / yrtDenoiseFrameBuffer, k_aux.h). launch_guides:
+// Denoise (yrtRenderGuides / yrtRenderAlbedo / yrtDenoiseFrameBuffer; k_firsthit.h, k_denoise.h). launch_guides:
 // the first-hit guide frames of a width x height view of `cam`, one thread per pixel:
 // pos4 = (hit point, t), nrm4 = (viewer-facing shading normal, 1); misses (0, 0, 0, inf) and 0.
 // albedo4 != null: the same pass also stores (first-hit albedo, 1), misses 0 (k_guides<true>).

@@ -12,7 +12,10 @@
 //   back-face filter (cullBackFaces meshes, shapes/trianglemesh_full.cpp:86-106): reject den <= 0
 //   closest hit: smallest (t, global triangle id) — order independent, so any BVH gives
 //   the same answer (used to pin the GPU against the oracle's own BVH).
-// Stack: per-lane short stack in LDS, [depth][lane] so a wave's pushes hit 64 distinct
+// One traversal: every kernel walks the 64-B quantized nodes (common/yrt_qnode.h) with the
+// pieces below: k_trace in its wavefront loop, the kernels off the render loop (k_firsthit.h)
+// through closest_hit. The float nodes are the builder's and the refit's, not a kernel's.
+// Stack (k_trace): per-lane short stack in LDS, [depth][lane] so a wave's pushes hit 64 distinct
 // banks. Only the top entries live in LDS, a ring of 16 per lane (4 KB per 64-lane block) for
 // every traversal kind since round 6; deeper entries spill to global memory. History: closest
 // hit on the float nodes, 32 entries instead of 16: +4.9 % on C3 in round 1, still +2 % in
@@ -82,62 +85,13 @@ struct RayPre {
   float tnear, tfar;
   V3 oi;         // org * inv (rounded): slab distances as fma(plane, inv, -oi) (box4_qdata)
   float margin;  // absolute slack of those distances: 2^-22 * max |oi| (see box4_qdata)
+  V3 oiLo;       // closest_hit only (box4_qdata<ANY, true>): org * inv - oi, exact
 };
 
 // Per-ray constants of box4_qdata's fused slab test.
 __device__ __forceinline__ void ray_slab_consts(const V3& org, const V3& inv, V3& oi, float& margin) {
   oi = v3(org.x * inv.x, org.y * inv.y, org.z * inv.z);
   margin = fmaxf(fmaxf(fabsf(oi.x), fabsf(oi.y)), fabsf(oi.z)) * 2.384185791015625e-07f;  // 2^-22
-}
-
-// Entry distances of the four children of a 4-wide node (INFINITY = missed / empty slot).
-// Slab distances (b - o) * inv are computed two children at a time with packed ops
-// (v_pk_add_f32 / v_pk_mul_f32); the robust factor widens the exit distance as before.
-__device__ __forceinline__ void box4(const GpuNode* __restrict__ np, const RayPre& r, float tmax, float t[4],
-                                     int c[4]) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  const float4* q = (const float4*)np;
-  const float4 lx = q[0], hx = q[1], ly = q[2], hy = q[3], lz = q[4], hz = q[5];
-  const int4 ch = *(const int4*)(q + 6);
-  const f2 ox = {r.org.x, r.org.x}, oy = {r.org.y, r.org.y}, oz = {r.org.z, r.org.z};
-  const f2 ix = {r.inv.x, r.inv.x}, iy = {r.inv.y, r.inv.y}, iz = {r.inv.z, r.inv.z};
-  f2 lx01 = (f2{lx.x, lx.y} - ox) * ix, lx23 = (f2{lx.z, lx.w} - ox) * ix;
-  f2 hx01 = (f2{hx.x, hx.y} - ox) * ix, hx23 = (f2{hx.z, hx.w} - ox) * ix;
-  f2 ly01 = (f2{ly.x, ly.y} - oy) * iy, ly23 = (f2{ly.z, ly.w} - oy) * iy;
-  f2 hy01 = (f2{hy.x, hy.y} - oy) * iy, hy23 = (f2{hy.z, hy.w} - oy) * iy;
-  f2 lz01 = (f2{lz.x, lz.y} - oz) * iz, lz23 = (f2{lz.z, lz.w} - oz) * iz;
-  f2 hz01 = (f2{hz.x, hz.y} - oz) * iz, hz23 = (f2{hz.z, hz.w} - oz) * iz;
-  const float INF = __int_as_float(0x7f800000);
-  // A direction component that safe_inv clamps (zero, or below 1e-20): the ray stays in its plane
-  // of that axis, so the slab is the whole line when the origin lies within [lo, hi], planes
-  // included, and empty otherwise (near = far = +INF: missed whenever another axis or tmax bounds
-  // the exit; a ray with all three components clamped hits no triangle anyway). The products
-  // alone put an origin exactly on a plane at distance 0 from it and cull the box lying behind
-  // that plane (a ray along a box face); the oracle's box_hit does the same.
-#define YRT_FLAT_IN(LO_, O, HI_) (((LO_) <= (O) && (O) <= (HI_)) ? -INF : INF)
-#define YRT_FLAT_AXIS(D, O, LO, HI, L01, L23, H01, H23)               \
-  if (!(fabsf(D) > 1e-20f)) {                                         \
-    L01 = f2{YRT_FLAT_IN(LO.x, O, HI.x), YRT_FLAT_IN(LO.y, O, HI.y)}; \
-    L23 = f2{YRT_FLAT_IN(LO.z, O, HI.z), YRT_FLAT_IN(LO.w, O, HI.w)}; \
-    H01 = H23 = f2{INF, INF};                                         \
-  }
-  YRT_FLAT_AXIS(r.dir.x, r.org.x, lx, hx, lx01, lx23, hx01, hx23)
-  YRT_FLAT_AXIS(r.dir.y, r.org.y, ly, hy, ly01, ly23, hy01, hy23)
-  YRT_FLAT_AXIS(r.dir.z, r.org.z, lz, hz, lz01, lz23, hz01, hz23)
-#undef YRT_FLAT_AXIS
-#undef YRT_FLAT_IN
-#define YRT_CHILD(k, LX, HX, LY, HY, LZ, HZ, CH)                                                          \
-  do {                                                                                                    \
-    const float nn = fmaxf(fmaxf(fminf(LX, HX), fminf(LY, HY)), fmaxf(fminf(LZ, HZ), r.tnear));          \
-    const float ff = fminf(fminf(fmaxf(LX, HX), fmaxf(LY, HY)), fminf(fmaxf(LZ, HZ), tmax));             \
-    t[k] = ((nn <= ff * YRT_BOX_ROBUST) && (CH) != -1) ? nn : INF;                                        \
-    c[k] = (CH);                                                                                          \
-  } while (0)
-  YRT_CHILD(0, lx01.x, hx01.x, ly01.x, hy01.x, lz01.x, hz01.x, ch.x);
-  YRT_CHILD(1, lx01.y, hx01.y, ly01.y, hy01.y, lz01.y, hz01.y, ch.y);
-  YRT_CHILD(2, lx23.x, hx23.x, ly23.x, hy23.x, lz23.x, hz23.x, ch.z);
-  YRT_CHILD(3, lx23.y, hx23.y, ly23.y, hy23.y, lz23.y, hz23.y, ch.w);
-#undef YRT_CHILD
 }
 
 // The wavefront kernel's box test picks the near/far plane of each axis per ray by the sign of
@@ -169,7 +123,8 @@ __device__ __forceinline__ int plane_offsets(float ix, float iy, float iz) {
 // child reference.
 // MISS: the entry distance reported for a missed child (+INF for closest-hit rays, which sort
 // ascending; -INF for any-hit rays, which visit the farthest child first, see sort3_far).
-// (The same test on the float nodes went with k_trace's float-node traversal, see DESIGN.md.)
+// (The same test on the float nodes went with k_trace's float-node traversal, and the min/max
+// one with its flat-axis case with the side kernels' own depth-first walk)
 // The quantized node as loaded (14 words).
 struct QNodeData {
   float4 h;   // origin xyz, quantum exponents
@@ -186,7 +141,18 @@ __device__ __forceinline__ QNodeData qnode_load(const GpuQNode* __restrict__ bas
   d.pb = *(const uint2*)(b0 + 48);
   return d;
 }
-template <bool ANY>
+// SPLIT (closest_hit): the ray also carries oiLo = org * inv - oi exactly (one FMA), and
+// a = fma(origin, inv, -oi) - oiLo. The rounding of org * inv is gone from the distances, what
+// is left of it is second order (u^2 |oi|), and so is the margin (ray_pre). Why: a camera ray
+// nearly parallel to an axis plane, from an origin far from 0 on that axis, has |oi| = |org / dir|
+// of 1e7 and more and a margin of several scene units: no box near the ray is culled any more.
+// On C3 at 2048 x 2048 the pixel whose |dir.y| is 2.6e-7 (margin 7.5) takes 220 node steps and
+// 478 triangle tests where its neighbours take 13 and 3; 11 pixels have a margin above 1.
+// k_trace's waves refill around such a lane; a kernel with one ray per lane for its whole
+// life (k_guides) ends when that lane does: 0.585 against 0.473 ms for the guide pass
+// (profiles/one_traversal_ab.txt). The results are the same bits either way: both tests are
+// conservative.
+template <bool ANY, bool SPLIT = false>
 __device__ __forceinline__ void box4_qdata(const QNodeData& d, const RayPre& r, int planeOff, float tmax, float t[4],
                                            int c[4]) {
   typedef float f2 __attribute__((ext_vector_type(2)));
@@ -198,9 +164,14 @@ __device__ __forceinline__ void box4_qdata(const QNodeData& d, const RayPre& r, 
   const float sx = __uint_as_float((ex & 0xffu) << 23) * r.inv.x;
   const float sy = __uint_as_float(((ex >> 8) & 0xffu) << 23) * r.inv.y;
   const float sz = __uint_as_float(((ex >> 16) & 0xffu) << 23) * r.inv.z;
-  const float ax = __builtin_fmaf(h.x, r.inv.x, -r.oi.x);
-  const float ay = __builtin_fmaf(h.y, r.inv.y, -r.oi.y);
-  const float az = __builtin_fmaf(h.z, r.inv.z, -r.oi.z);
+  float ax = __builtin_fmaf(h.x, r.inv.x, -r.oi.x);
+  float ay = __builtin_fmaf(h.y, r.inv.y, -r.oi.y);
+  float az = __builtin_fmaf(h.z, r.inv.z, -r.oi.z);
+  if constexpr (SPLIT) {
+    ax -= r.oiLo.x;
+    ay -= r.oiLo.y;
+    az -= r.oiLo.z;
+  }
   const bool hx = (planeOff & 16) != 0, hy = (planeOff & (16 << 8)) != 0, hz = (planeOff & (16 << 16)) != 0;
   const uint32_t nwx = hx ? pa.y : pa.x, fwx = hx ? pa.x : pa.y;
   const uint32_t nwy = hy ? pa.w : pa.z, fwy = hy ? pa.z : pa.w;
@@ -237,10 +208,10 @@ __device__ __forceinline__ void box4_qdata(const QNodeData& d, const RayPre& r, 
   YRT_CHILD(3, nx23.y, fx23.y, ny23.y, fy23.y, nz23.y, fz23.y, ch.w);
 #undef YRT_CHILD
 }
-template <bool ANY>
+template <bool ANY, bool SPLIT = false>
 __device__ __forceinline__ void box4_quant(const RayPre& r, int planeOff, float tmax, float t[4], int c[4],
                                            const GpuQNode* __restrict__ base, int nodeIdx) {
-  box4_qdata<ANY>(qnode_load(base, nodeIdx), r, planeOff, tmax, t, c);
+  box4_qdata<ANY, SPLIT>(qnode_load(base, nodeIdx), r, planeOff, tmax, t, c);
 }
 
 // Sorts the four (t, child) pairs by t ascending (5-comparator network, stable for equal t).
@@ -325,41 +296,45 @@ __device__ __forceinline__ bool tri_test_g(const GpuTri& tr, const RayPre& r, fl
 // returned undivided: u = U/absDen, v = V/absDen are only needed for an accepted hit.
 __device__ __forceinline__ bool tri_test_t(const GpuTri& tr, const RayPre& r, float tfar, float& t, float& U_,
                                            float& V_, float& absDen_) {
-  V3 v0 = v3(tr.v0[0], tr.v0[1], tr.v0[2]);
-  V3 e1 = v3(tr.e1[0], tr.e1[1], tr.e1[2]);
-  V3 e2 = v3(tr.e2[0], tr.e2[1], tr.e2[2]);
-  V3 Ng = tri_cross(e1, e2);
-  V3 C = v0 - r.org;
-  V3 R = tri_cross(r.dir, C);
-  float den = tri_dot(Ng, r.dir);
-  float absDen = fabsf(den);
-  float sgn = den < 0.0f ? -1.0f : 1.0f;
-  float U = tri_dot(R, e2) * sgn;
-  float V = tri_dot(R, e1) * sgn;
-  bool ok = (den != 0.0f) & (U >= 0.0f) & (V >= 0.0f) & (U + V <= absDen);
-  int flags = __float_as_int(tr.e1[3]);
-  ok &= !((flags & 1) && !(den > 0.0f));
-  float T = tri_dot(Ng, C) * sgn;
-  t = T / absDen;
-  ok &= (t > r.tnear) & (t < tfar);
-  U_ = U;
-  V_ = V;
-  absDen_ = absDen;
-  return ok;
+  const bool g = tri_test_g(tr, r, t, U_, V_, absDen_);
+  return g & (t > r.tnear) & (t < tfar);
 }
 
-// Plain depth-first traversal (rtPick, DebugRenderer): nearest child first, the other hit
-// children pushed farthest-first; same closest-hit rule as the wavefront kernel.
-template <bool ANY>
-__device__ __forceinline__ Hit traverse(const GpuNode* __restrict__ nodes, const GpuTri* __restrict__ tris,
-                                        const RayPre& r, int* __restrict__ stack /* LDS, unused */) {
-  (void)stack;
+// The per-ray constants of a traversal on the quantized nodes, as k_trace computes them when a
+// lane takes a ray: the reciprocal direction, box4_qdata's slab constants and the plane picks;
+// and for box4_qdata<ANY, true> the exact remainder of org * inv, with the margin that is left:
+// the distances' error from org * inv is now at most u |a| (a's second rounding, covered like
+// its first by the quantum the planes lie outside, yrt_qnode.h) + u^2 |oi|; 2^-46 |oi| is 4 u^2.
+__device__ __forceinline__ RayPre ray_pre(const V3& org, const V3& dir, float tnear, float tfar, int& planeOff) {
+  RayPre r;
+  r.org = org;
+  r.dir = dir;
+  r.inv = v3(safe_inv(dir.x), safe_inv(dir.y), safe_inv(dir.z));
+  r.tnear = tnear;
+  r.tfar = tfar;
+  ray_slab_consts(org, r.inv, r.oi, r.margin);
+  r.oiLo = v3(__builtin_fmaf(org.x, r.inv.x, -r.oi.x), __builtin_fmaf(org.y, r.inv.y, -r.oi.y),
+              __builtin_fmaf(org.z, r.inv.z, -r.oi.z));
+  r.margin *= 5.9604644775390625e-08f;  // 2^-22 |oi| -> 2^-46 |oi|
+  planeOff = plane_offsets(r.inv.x, r.inv.y, r.inv.z);
+  return r;
+}
+
+// One lane's closest hit by plain depth-first traversal (rtPick, the DebugRenderer, the
+// denoiser's guides; off the render loop, the stack is private): k_trace's pieces in k_trace's
+// order — box4_quant against the closest hit so far, the nearest child next and the other hit
+// children pushed farthest first, tri_test_g, and the same rule: the smallest (t, triangle id)
+// within (tnear, tfar). Worded as in k_trace's leaf step; the two stay the same rule.
+__device__ __forceinline__ Hit closest_hit(const GpuQNode* __restrict__ qnodes, const GpuTri* __restrict__ tris,
+                                           const V3& org, const V3& dir, float tnear, float tfar) {
   Hit best;
-  best.t = r.tfar;
+  best.t = tfar;
   best.u = best.v = 0.0f;
   best.tri = -1;
   // NaN tfar (tMaxShadowRay = inf): every comparison is false, no hit.
-  if (!(r.tfar >= r.tnear)) return best;
+  if (!(tfar >= tnear)) return best;
+  int planeOff;
+  const RayPre r = ray_pre(org, dir, tnear, tfar, planeOff);
   int pst[YRT_STACK_DEPTH];
   int sp = 0;
   int cur = 0;  // (index << 5) | count
@@ -367,7 +342,7 @@ __device__ __forceinline__ Hit traverse(const GpuNode* __restrict__ nodes, const
     if ((cur & 31) == 0) {
       float t[4];
       int c[4];
-      box4(nodes + (cur >> 5), r, best.t, t, c);
+      box4_quant<false, true>(r, planeOff, best.t, t, c, qnodes, cur >> 5);
       sort4(t, c);
       const float INF = __int_as_float(0x7f800000);
       if (t[3] < INF) pst[sp++] = c[3];
@@ -382,23 +357,12 @@ __device__ __forceinline__ Hit traverse(const GpuNode* __restrict__ nodes, const
       for (int i = 0; i < cnt; ++i) {
         const GpuTri tr = tris[idx + i];
         float t, U, V, absDen;
-        bool ok = tri_test_t(tr, r, ANY ? r.tfar : best.t + 0.0f, t, U, V, absDen);
-        int gid = __float_as_int(tr.v0[3]);
-        if (ANY) {
-          if (ok) {
-            best.t = t; best.u = U / absDen; best.v = V / absDen; best.tri = gid;
-            return best;
-          }
-        } else {
-          // strict (t < best) or tie with smaller id; tri_test used tfar = best.t so ties
-          // (t == best.t) were rejected: re-test them against the original tfar.
-          if (!ok && best.tri >= 0 && t == best.t && gid < best.tri) {
-            float t2, U2, V2, a2;
-            ok = tri_test_t(tr, r, r.tfar, t2, U2, V2, a2);
-          }
-          if (ok) {
-            best.t = t; best.u = U / absDen; best.v = V / absDen; best.tri = gid;
-          }
+        const bool g = tri_test_g(tr, r, t, U, V, absDen);
+        const int gid = __float_as_int(tr.v0[3]);
+        // a tie with an accepted hit (best.tri >= 0, so best.t < tfar) is within the range
+        const bool tie = (t == best.t) & (best.tri >= 0) & (gid < best.tri);
+        if (g & (t > tnear) & ((t < best.t + 0.0f) | tie)) {
+          best.t = t; best.u = U / absDen; best.v = V / absDen; best.tri = gid;
         }
       }
     }
