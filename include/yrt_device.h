@@ -329,7 +329,9 @@ YRT_API int64_t yrtGetCapturedRays(YRTDevice dev, int shadow, int depth, float* 
 YRT_API int yrtDebugTraceProfile(YRTDevice dev, uint64_t* out8, int reset);
 /* Arithmetic self-check on the device: fn 0 compares the kernels' correctly rounded fast
  * reciprocal (rcp_rn, common/yrt_math.h) with the IEEE division 1.0f/x for all 2^32 inputs.
- * out2[0] = mismatches, out2[1] = the smallest mismatching input (or UINT64_MAX). */
+ * out2[0] = mismatches, out2[1] = the smallest mismatching input (or UINT64_MAX).
+ * fn 3 / 4: the emulated rcpps / rsqrtps (common/yrt_sse_rcp.h) of given inputs: out2[0] = their
+ * count n (at most 2^20), out2[1 .. n] = the inputs' bits, replaced by the results' bits. */
 YRT_API int yrtDebugCheckMath(YRTDevice dev, int fn, uint64_t* out2);
 /* Arithmetic self-check of the emulated SSE estimates the reference's rcp/rsqrt start from
  * (common/yrt_sse_rcp.h; common/math/math.h:38-59): fn 1 rcpps, fn 2 rsqrtps, each against its
@@ -347,6 +349,18 @@ YRT_API int yrtDebugCheckMathTable(YRTDevice dev, int fn, const uint16_t* table2
  * with c; every index in the rows is checked before the launch. Not part of the renderer. */
 YRT_API int yrtDebugShade(YRTDevice dev, int mode, YRTHandle object, const float* rows, int n, const void* materials,
                           int numMaterials, float* out);
+/* Test-only: the direction-term table of a sample table (kernels/k_sample_dirs.h). The frame
+ * cache entry of the request (spp, sets, iteration, num1D, num2D, filter; no lights) is created
+ * on the device's first GPU as a render would create it; dims receives its sample table
+ * (yrtDebugSampleTable's layout) and dirs4 its table of (cosPhi, sinPhi, cosTheta, sinTheta),
+ * [num2D][records] x 4 floats, read back from the device. Returns the record count (sets * spp
+ * rounded up to a power of two); a buffer too small for its table is left untouched. */
+YRT_API int yrtDebugSampleDirs(YRTDevice dev, int spp, int sets, int iteration, int num1D, int num2D,
+                               const char* filter, float* dims, size_t dimsFloats, float* dirs4, size_t dirsFloats);
+/* Test-only: the same four terms of n samples (u[i], v[i]) into out4 (n x 4 floats). mode 0: a
+ * probe kernel that spells them out per sample as the samplers did before the table; mode 1: the
+ * table's own kernel over the samples as one slot of n records. */
+YRT_API int yrtDebugDirTerms(YRTDevice dev, int mode, const float* u, const float* v, int n, float* out4);
 /* The image tile that logical tile t of a sharded job's frame of T tiles covers
  * (common/yrt_tile_scatter.h: a fixed bijection of [0, T), used by the renderer and the gather
  * whenever the tile stride is above 1). Host-side; -1 for t outside [0, T). */

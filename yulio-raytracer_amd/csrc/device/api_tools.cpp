@@ -206,7 +206,7 @@ int yrtDebugPixelSamples(YRTDevice dev, int pixelId, int frame, float* out4, int
 
 int yrtDebugCheckMath(YRTDevice dev, int fn, uint64_t* out2) {
   DEV_GUARD(dev, -1)
-  if (fn != 0 || !out2) throw std::runtime_error("yrtDebugCheckMath: fn 0 only");
+  if ((fn != 0 && fn != 3 && fn != 4) || !out2) throw std::runtime_error("yrtDebugCheckMath: fn 0, 3 or 4");
   HIP_CHECK(hipSetDevice(dev->d->hipDevice));
   if (check_math(fn, (unsigned long long*)out2) != 0) throw std::runtime_error("check_math failed");
   return 0;
@@ -218,6 +218,39 @@ int yrtDebugCheckMathTable(YRTDevice dev, int fn, const uint16_t* table2048, uin
   if ((fn != 1 && fn != 2) || !table2048 || !out2) throw std::runtime_error("yrtDebugCheckMathTable: fn 1 or 2");
   HIP_CHECK(hipSetDevice(dev->d->hipDevice));
   if (check_math_table(fn, table2048, (unsigned long long*)out2) != 0) throw std::runtime_error("check_math_table failed");
+  return 0;
+  DEV_END(-1)
+}
+
+int yrtDebugSampleDirs(YRTDevice dev, int spp, int sets, int iteration, int num1D, int num2D, const char* filter,
+                       float* dims, size_t dimsFloats, float* dirs4, size_t dirsFloats) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  if (!D.gpu) throw std::runtime_error("yrtDebugSampleDirs: host-only device");
+  if (spp < 1 || sets < 1 || iteration < 0 || num1D < 0 || num2D < 0)
+    throw std::runtime_error("yrtDebugSampleDirs: invalid arguments");
+  HIP_CHECK(hipSetDevice(D.ctx[0]->hipDevice));
+  SampleRequest req;
+  req.spp = spp;
+  req.sets = sets;
+  req.iteration = iteration;
+  req.num1D = num1D;
+  req.num2D = num2D;
+  req.filter = filter ? filter : "bspline";
+  const FrameCache& fc = frame_cache(*D.ctx[0], req, 0);
+  const SampleTable& t = fc.table;
+  const size_t nd = (size_t)num2D * t.numRecords * 4;
+  if (dims && dimsFloats >= t.dims.size()) memcpy(dims, t.dims.data(), t.dims.size() * sizeof(float));
+  if (dirs4 && nd && dirsFloats >= nd) HIP_CHECK(hipMemcpy(dirs4, fc.dirs.p, nd * sizeof(float), hipMemcpyDeviceToHost));
+  return t.numRecords;
+  DEV_END(-1)
+}
+
+int yrtDebugDirTerms(YRTDevice dev, int mode, const float* u, const float* v, int n, float* out4) {
+  DEV_GUARD(dev, -1)
+  if (!dev->d->gpu) throw std::runtime_error("yrtDebugDirTerms: host-only device");
+  HIP_CHECK(hipSetDevice(dev->d->hipDevice));
+  if (check_dir_terms(mode, n, u, v, out4) != 0) throw std::runtime_error("yrtDebugDirTerms: invalid arguments or HIP error");
   return 0;
   DEV_END(-1)
 }

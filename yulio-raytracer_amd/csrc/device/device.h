@@ -36,6 +36,7 @@ struct FrameCache {
   std::string key;
   SampleTable table;
   DevBuf dims, light;
+  DevBuf dirs;  // the direction terms of the table's 2-D samples (k_sample_dirs), [num2D][numRecords] float4
   std::vector<uint8_t> slotLive;  // per light-sample slot: some record's radiance is not exactly 0
 };
 
@@ -224,6 +225,9 @@ struct GpuCtx {
     }
   }
 };
+
+// the request's sample table on g (GpuCtx::fcaches), built and uploaded at its first use (render.cpp)
+FrameCache& frame_cache(GpuCtx& g, const SampleRequest& req, uint64_t sceneSerial);
 
 // the tiles of shard (index, count): tile = index + j * count, j < shard_tiles
 inline int shard_tiles(int numTiles, int index, int count) {

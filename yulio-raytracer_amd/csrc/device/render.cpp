@@ -220,7 +220,7 @@ static GpuRenderParams render_params(const RendererObj& R, const ToneMapperObj& 
 }
 
 // the request's sample table on g (GpuCtx::fcaches), built and uploaded at its first use
-static FrameCache& frame_cache(GpuCtx& g, const SampleRequest& req, uint64_t sceneSerial) {
+FrameCache& frame_cache(GpuCtx& g, const SampleRequest& req, uint64_t sceneSerial) {
   char keybuf[256];
   snprintf(keybuf, sizeof(keybuf), "%d/%d/%d/%d/%d/%s/%llu", req.spp, req.sets, req.iteration, req.num1D, req.num2D,
            req.filter.c_str(), (unsigned long long)sceneSerial);
@@ -241,6 +241,12 @@ static FrameCache& frame_cache(GpuCtx& g, const SampleRequest& req, uint64_t sce
       }
     fc->dims.upload(fc->table.dims);
     fc->light.upload(fc->table.light);
+    // the direction terms of the 2-D samples, computed on the device from the uploaded rows; the
+    // lanes' streams read them, so the table is complete before the entry is used
+    fc->dirs.alloc(sizeof(float4) * std::max<size_t>(1, (size_t)req.num2D * t.numRecords));
+    launch_sample_dirs(fc->dims.as<float>() + (size_t)(5 + req.num1D) * t.numRecords, t.numRecords, req.num2D,
+                       fc->dirs.as<float4>(), g.stream);
+    HIP_CHECK(hipStreamSynchronize(g.stream));
     fc->key = keybuf;
     g.fcacheOrder.push_back(keybuf);
     fit = g.fcaches.emplace(keybuf, std::move(fc)).first;
@@ -304,6 +310,7 @@ static FrameView frame_view(GpuCtx& g, const RendererObj& R, const FrameCache& f
   fv.cam = g.dCam.as<GpuCamera>();
   fv.samples = fcache.dims.as<float>();
   fv.lightSamples = fcache.light.as<float>();
+  fv.sampleDirs = fcache.dirs.as<float4>();
   fv.pixelSets = g.dPixelSets.as<uint8_t>();
   fv.numRecords = tab.numRecords;
   fv.numLightSlots = std::max(1, tab.numLightSlots);

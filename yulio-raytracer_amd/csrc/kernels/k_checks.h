@@ -69,6 +69,15 @@ __global__ __launch_bounds__(256) void k_check_math_table(int fn, const uint16_t
   }
 }
 
+// fn 3 / 4: yrt_rcpps / yrt_rsqrtps of n given inputs, bits in and bits out in place (the special
+// inputs of tests/test_sse_rcp_special.py against the host's emulation)
+__global__ __launch_bounds__(256) void k_check_math_values(int fn, int n, unsigned long long* io) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float x = __uint_as_float((uint32_t)io[i]);
+  io[i] = __float_as_uint(fn == 3 ? yrt_rcpps(x) : yrt_rsqrtps(x));
+}
+
 // ---------------------------------------------------------------- shading-layer probe
 // k_check_shade (yrtDebugShade, test-only): one thread per row calls the device functions of the
 // shading layer as they stand, so that their results can be compared bit for bit with the
@@ -107,6 +116,7 @@ __global__ __launch_bounds__(64) void k_check_shade(int mode, int n, const float
   dg.illumMask = dg.shadowMask = -1;
   dg_frame(dg);
   const float sx = r[18], sy = r[19], ss = r[20];
+  const float4 sd = sample_dir(sx, sy);  // as k_sample_dirs tabulates it for k_shade
   BRDFSet bs;
   bs.n = __float_as_int(r[21]);
 #pragma unroll
@@ -122,19 +132,19 @@ __global__ __launch_bounds__(64) void k_check_shade(int mode, int n, const float
   float pdf = 0.f;
   if (mode == 0) {
     a = comp_eval<CM>(bs.c[0], mats, wo, dg, wi);
-    b = comp_sample<CM>(bs.c[0], mats, wo, dg, sx, sy, w, pdf);
+    b = comp_sample<CM>(bs.c[0], mats, wo, dg, sd, sy, w, pdf);
     o[9] = pdf;
     o[10] = o[11] = 0.f;
   } else if (mode == 1) {
     uint32_t type = 0;
-    a = set_sample<CM>(bs, mats, wo, dg, sx, sy, ss, b, pdf, type, st + threadIdx.x);
+    a = set_sample<CM>(bs, mats, wo, dg, sd, sy, ss, b, pdf, type, st + threadIdx.x);
     o[6] = pdf;
     o[7] = __uint_as_float(type);
     o[8] = o[9] = o[10] = o[11] = 0.f;
   } else if (mode == 2) {
     camera_ray(*cam, r[0], r[1], a, b, sx, sy);
   } else {
-    a = light_sample<kAllLights>(*light, dg, sx, sy, b, pdf);
+    a = light_sample<kAllLights>(*light, dg, sd, sx, sy, b, pdf);
     o[6] = pdf;
     o[7] = o[8] = o[9] = o[10] = o[11] = 0.f;
   }

@@ -197,7 +197,8 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
     V3 nwi = v3s(0.f), nthr = v3s(0.f);
     int nmeta = 0;
     bool doSample = false;
-    float sx = 0.f, sy = 0.f, ss = 0.f;
+    float4 sd = make_float4(0.f, 0.f, 0.f, 0.f);
+    float sy = 0.f, ss = 0.f;
     if (active && isHit) {
       bool stop = depth >= rp.maxDepth - 1;
       if (!stop && rp.rrDepth > 0 && depth >= rp.rrDepth - 1) {  // size_t compare in the reference
@@ -206,8 +207,10 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
       }
       if (!stop) {
         const int d2 = rp.firstScatterSampleID + depth;
-        sx = samp(fv, 5 + rp.dim1D + 2 * d2, rec);
-        sy = samp(fv, 5 + rp.dim1D + 2 * d2 + 1, rec);
+        // the 2-D sample's tabulated terms in place of its first coordinate; the second one
+        // only where a power-cosine sampler can read it
+        sd = samp_dir(fv, d2, rec);
+        if constexpr ((comps_of(MM) & kCompsRawSy) != 0u) sy = samp(fv, 5 + rp.dim1D + 2 * d2 + 1, rec);
         ss = samp(fv, 5 + rp.firstScatterTypeSampleID + depth, rec);
         doSample = true;
       }
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
     uint32_t stype = 0;
     V3 sc = v3s(0.f);
     if (doSample)
-      sc = set_sample<comps_of(MM)>(bs, sv.materials, wo, dg, sx, sy, ss, nwi, spdf, stype, sstash + threadIdx.x);
+      sc = set_sample<comps_of(MM)>(bs, sv.materials, wo, dg, sd, sy, ss, nwi, spdf, stype, sstash + threadIdx.x);
     SPROF_FINE(1);  // CompositedBRDF::sample
     if (doSample) {
       {
@@ -270,9 +273,16 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
           pdf = ls[3];
           Ls = v3(ls[4], ls[5], ls[6]);
         } else {
-          const float lsx = samp(fv, 5 + rp.dim1D + 2 * rp.lightSampleID, rec);
-          const float lsy = samp(fv, 5 + rp.dim1D + 2 * rp.lightSampleID + 1, rec);
-          Ls = light_sample<lights_of<MM>()>(lt, dg, lsx, lsy, wi, pdf);
+          // the light's type is wave-uniform: the dome light loads the sample's tabulated terms,
+          // the triangle light its raw coordinates, the distant light both
+          float4 lsd = make_float4(0.f, 0.f, 0.f, 0.f);
+          float lsx = 0.f, lsy = 0.f;
+          if ((1u << lt.type) & kLightsDir) lsd = samp_dir(fv, rp.lightSampleID, rec);
+          if ((lights_of<MM>() & kLightsRawS) != 0u && ((1u << lt.type) & kLightsRawS)) {
+            lsx = samp(fv, 5 + rp.dim1D + 2 * rp.lightSampleID, rec);
+            lsy = samp(fv, 5 + rp.dim1D + 2 * rp.lightSampleID + 1, rec);
+          }
+          Ls = light_sample<lights_of<MM>()>(lt, dg, lsd, lsx, lsy, wi, pdf);
         }
       }
       SPROF_FINE(3);  // Light::sample

@@ -32,6 +32,7 @@
 #include "k_denoise.h"
 #include "k_tiles.h"
 #include "k_checks.h"
+#include "k_sample_dirs.h"
 #include "k_refit.h"
 
 namespace yrt {
@@ -43,6 +44,12 @@ static inline int grid_for(long long n, int block, int maxBlocks) {
   if (g < 1) g = 1;
   if (g > maxBlocks) g = maxBlocks;
   return (int)g;
+}
+
+void launch_sample_dirs(const float* pairs, int numRecords, int numSlots, float4* out, hipStream_t s) {
+  const int n = numSlots * numRecords;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_sample_dirs, dim3((n + 255) / 256), dim3(256), 0, s, pairs, numRecords, numSlots, out);
 }
 
 void launch_pixel_sets(const FrameView& fv, uint8_t* pixelSets, int width, int height, int sets, hipStream_t s) {
@@ -246,7 +253,47 @@ int check_shade(int mode, int n, const float* rows, const GpuMaterial* mats, int
   return rc;
 }
 
+int check_dir_terms(int mode, int n, const float* u, const float* v, float* out4) {
+  if ((mode != 0 && mode != 1) || n < 1 || !u || !v || !out4) return -1;
+  float* dIn = nullptr;  // the u row, then the v row
+  float4* dOut = nullptr;
+  const size_t rowBytes = (size_t)n * sizeof(float);
+  int rc = 0;
+  if (hipMalloc(&dIn, 2 * rowBytes) != hipSuccess || hipMalloc(&dOut, (size_t)n * sizeof(float4)) != hipSuccess) rc = -1;
+  if (!rc && (hipMemcpy(dIn, u, rowBytes, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(dIn + n, v, rowBytes, hipMemcpyHostToDevice) != hipSuccess))
+    rc = -1;
+  if (!rc) {
+    if (mode == 0)
+      hipLaunchKernelGGL(k_check_dir_terms, dim3((n + 63) / 64), dim3(64), 0, 0, dIn, dIn + n, n, dOut);
+    else
+      launch_sample_dirs(dIn, n, 1, dOut, 0);
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(out4, dOut, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = -1;
+  }
+  (void)hipFree(dOut);
+  (void)hipFree(dIn);
+  return rc;
+}
+
 int check_math(int fn, unsigned long long* host2) {
+  if (fn == 3 || fn == 4) {
+    // host2[0] = n, host2[1 .. n] = the inputs' bits, replaced by the results' bits
+    const unsigned long long n = host2[0];
+    if (n < 1 || n > kCheckMathMaxValues) return -1;
+    unsigned long long* d = nullptr;
+    if (hipMalloc(&d, n * 8) != hipSuccess) return -1;
+    int rc = hipMemcpy(d, host2 + 1, n * 8, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+    if (!rc) {
+      hipLaunchKernelGGL(k_check_math_values, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, fn, (int)n, d);
+      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host2 + 1, d, n * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = -1;
+    }
+    (void)hipFree(d);
+    return rc;
+  }
+  if (fn != 0) return -1;
   unsigned long long* d = nullptr;
   if (hipMalloc(&d, 16) != hipSuccess) return -1;
   const unsigned long long init[2] = {0ull, ~0ull};

@@ -143,5 +143,9 @@ __device__ __forceinline__ bool batch_pixel(const RP& rp, const BatchInfo& bi, i
 __device__ __forceinline__ float samp(const FrameView& fv, int dim, int rec) {
   return fv.samples[(size_t)dim * fv.numRecords + rec];
 }
+// the tabulated direction terms (sample_dir, yrt_shade.h) of record rec's 2-D sample `slot`
+__device__ __forceinline__ float4 samp_dir(const FrameView& fv, int slot, int rec) {
+  return fv.sampleDirs[(size_t)slot * fv.numRecords + rec];
+}
 
 }  // namespace yrt

@@ -65,6 +65,9 @@ struct FrameView {
   int numRecords, numLightSlots;
   GpuImage backplate;           // PathTraceIntegrator backplate (offset 0 in backplateTexels)
   const uint8_t* backplateTexels;  // null: none
+  // [rp->dim2D][numRecords]: (cosPhi, sinPhi, cosTheta, sinTheta) of every 2-D sample
+  // (sample_dir, yrt_shade.h), filled by k_sample_dirs when the table is uploaded
+  const float4* sampleDirs;
 };
 
 // Queues are split into YRT_QSEGS segments, each with its own append counter on its own
@@ -156,6 +159,9 @@ struct PrimaryRays {
 };
 
 // Kernel launchers (kernels/pathtrace.hip)
+// the direction-term table of a sample table's 2-D rows (k_sample_dirs.h): pairs =
+// [2 * numSlots][numRecords] floats, out = [numSlots][numRecords] float4, device pointers
+void launch_sample_dirs(const float* pairs, int numRecords, int numSlots, float4* out, hipStream_t s);
 void launch_pixel_sets(const FrameView& fv, uint8_t* pixelSets, int width, int height, int sets, hipStream_t s);
 void launch_raygen(const FrameView& fv, const PathBuffers& pb, const BatchInfo& bi, hipStream_t s);
 // counts: first segment counter of the queue (segments YRT_QCSTRIDE apart), numSegs segments
@@ -184,13 +190,19 @@ int trace_profile(unsigned long long* out8, int reset);
 // Debug capture: per-sample radiance of pixel id (y * width + x) of frame `frame` written to
 // out[s] by the next resolves (pixelId -1: off)
 int debug_pixel_capture(int pixelId, int frame, float4* out, int capacity);
-// Arithmetic self-check of the correctly rounded fast reciprocal (rcp_rn): see k_checks.h
+// Arithmetic self-check of the correctly rounded fast reciprocal (rcp_rn): see k_checks.h.
+// fn 3 / 4: yrt_rcpps / yrt_rsqrtps of host2[0] <= kCheckMathMaxValues inputs, host2[1 ..] in place
+constexpr unsigned long long kCheckMathMaxValues = 1ull << 20;
 int check_math(int fn, unsigned long long* host2);
 int check_math_table(int fn, const uint16_t* table2048, unsigned long long* host2);
 // Shading-layer probe (k_check_shade, k_checks.h; test-only): n rows of 48 words in, 12 words out,
 // host pointers; mats numMats records (may be null), cam / light one host record for modes 2 / 3
 int check_shade(int mode, int n, const float* rows, const GpuMaterial* mats, int numMats, const GpuCamera* cam,
                 const GpuLight* light, float* out);
+// Direction-term probe (k_sample_dirs.h; test-only): the terms of n samples (u[i], v[i]) into
+// out4 (n x 4 floats), host pointers. mode 0: spelled out per sample (k_check_dir_terms);
+// mode 1: k_sample_dirs over the samples as one slot of n records
+int check_dir_terms(int mode, int n, const float* u, const float* v, float* out4);
 // Multi-GPU gather (device/gather_device.cpp): the pixels of the tiles of one shard (job tile =
 // tileOffset + j * tileStride, j < numTiles, over numFrames stacked frames of tilesPerFrame
 // tiles) as a slab of numTiles * 256 elements in tile order j and scan order within the tile;

@@ -73,6 +73,9 @@ __host__ __device__ constexpr unsigned comps_of(unsigned mats) {
          ((mats & mat_bit(12)) ? (comp_bit(12) | comp_bit(13)) : 0u) |                              // Velvet
          ((mats & mat_bit(13)) ? (comp_bit(1) | comp_bit(4) | comp_bit(15)) : 0u);                  // MetallicPaint+glitter
 }
+// the components whose sample() reads the raw second coordinate of the 2-D sample (the
+// power-cosine samplers' yrt_powf(s.y, ...)); the others take the tabulated terms alone
+constexpr unsigned kCompsRawSy = comp_bit(5) | comp_bit(7) | comp_bit(10) | comp_bit(11) | comp_bit(15);
 #define YRT_ALL_MATS 0x3FFEu
 // Light types ride in bits 16.. of the same instantiation mask (bit 16 + LIGHT_x).
 __host__ __device__ constexpr unsigned light_bit(int t) { return 1u << (16 + t); }
@@ -162,11 +165,18 @@ __device__ __forceinline__ void dg_frame(DG& dg) {
   dg.Fy = F.vy;
 }
 __device__ __forceinline__ L3 dg_F(const DG& dg) { return l3(dg.Fx, dg.Fy, dg.Ns); }
-// cosineSampleHemisphere(u, v, dg.Ns) with the vertex's prebuilt frame
-__device__ __forceinline__ V3 cosine_hemi_dg(float u, float v, const DG& dg, float& pdf) {
+// The terms of a 2-D sample (u, v) that every direction sampler starts from and that do not
+// depend on the vertex: (cosPhi, sinPhi, cosTheta, sinTheta) = (cos 2πu, sin 2πu, √v, √(1 − v)).
+// k_sample_dirs tabulates them per (2-D slot, sample record) when a frame's sample table is
+// uploaded (FrameView::sampleDirs); the shading probe builds them per row with this function.
+__device__ __forceinline__ float4 sample_dir(float u, float v) {
   const float phi = kTwoPi * u;
-  const float cosTheta = sqrtf(v), sinTheta = sqrtf(1.0f - v);
-  V3 l = v3(yrt_cosf(phi) * sinTheta, yrt_sinf(phi) * sinTheta, cosTheta);
+  return make_float4(yrt_cosf(phi), yrt_sinf(phi), sqrtf(v), sqrtf(1.0f - v));
+}
+// cosineSampleHemisphere(u, v, dg.Ns) with the vertex's prebuilt frame, sd = sample_dir(u, v)
+__device__ __forceinline__ V3 cosine_hemi_dg(float4 sd, const DG& dg, float& pdf) {
+  const float cosTheta = sd.z, sinTheta = sd.w;
+  V3 l = v3(sd.x * sinTheta, sd.y * sinTheta, cosTheta);
   pdf = cosTheta * kOneOverPi;
   return mul(dg_F(dg), l);
 }
@@ -416,14 +426,15 @@ __device__ __forceinline__ V3 comp_eval(const Comp c, const GpuMaterial* __restr
   return v3s(0.0f);
 }
 
-// BRDF::sample of one component; returns color, sets wi/pdf.
+// BRDF::sample of one component at the 2-D sample s; returns color, sets wi/pdf. sd =
+// sample_dir(s.x, s.y); sy = s.y, read by the power-cosine samplers only (kCompsRawSy).
 template <unsigned CM>
 __device__ __forceinline__ V3 comp_sample(const Comp c, const GpuMaterial* __restrict__ mats, V3 wo, const DG& dg,
-                                          float sx, float sy, V3& wi, float& pdf) {
+                                          float4 sd, float sy, V3& wi, float& pdf) {
   switch (c.kind) {
     case C_LAMBERT: {
       YRT_IF_NOT(C_LAMBERT) break;
-      wi = cosine_hemi_dg(sx, sy, dg, pdf);
+      wi = cosine_hemi_dg(sd, dg, pdf);
       return lambert_eval(c.R, dg, wi);
     }
     case C_DIEL_REFL: {
@@ -461,7 +472,7 @@ __device__ __forceinline__ V3 comp_sample(const Comp c, const GpuMaterial* __res
       V3 wo1;
       refract5(wo, dg.Ns, c.a, cosThetaO, cosThetaO1, wo1);
       float pdf1;
-      V3 wi1 = cosine_hemi_dg(sx, sy, dg, pdf1);
+      V3 wi1 = cosine_hemi_dg(sd, dg, pdf1);
       V3 Fg = lambert_eval(c.R, dg, wi1);
       float cosThetaI1 = dot(wi1, dg.Ns);
       if (cosThetaI1 <= 0.0f) return v3s(0.0f);
@@ -481,9 +492,8 @@ __device__ __forceinline__ V3 comp_sample(const Comp c, const GpuMaterial* __res
       if (dot(wo, dg.Ns) <= 0.0f) return v3s(0.0f);
       const float n = c.c;
       const float norm1 = (n + 1) * kOneOverTwoPi;
-      const float phi = kTwoPi * sx;
-      const float cosPhi = yrt_cosf(phi);
-      const float sinPhi = yrt_sinf(phi);
+      const float cosPhi = sd.x;
+      const float sinPhi = sd.y;
       const float cosTheta = yrt_powf(sy, rcpf_(n + 1));
       const float sinTheta = cos2sin(cosTheta);
       V3 wh = mul(dg_F(dg), v3(cosPhi * sinTheta, sinPhi * sinTheta, cosTheta));
@@ -500,9 +510,8 @@ __device__ __forceinline__ V3 comp_sample(const Comp c, const GpuMaterial* __res
       if (dot(wo, dg.Ns) <= 0.0f) return v3s(0.0f);
       const float n = c.a;
       const float norm1 = (n + 1) * kOneOverTwoPi;
-      const float phi = kTwoPi * sx;
-      const float cosPhi = yrt_cosf(phi);
-      const float sinPhi = yrt_sinf(phi);
+      const float cosPhi = sd.x;
+      const float sinPhi = sd.y;
       const float cosTheta = yrt_powf(sy, rcpf_(n + 1));
       const float sinTheta = cos2sin(cosTheta);
       V3 wh = mul(dg_F(dg), v3(cosPhi * sinTheta, sinPhi * sinTheta, cosTheta));
@@ -519,9 +528,8 @@ __device__ __forceinline__ V3 comp_sample(const Comp c, const GpuMaterial* __res
       if (dot(wo, dg.Ns) <= 0.0f) return v3s(0.0f);
       const float nx = c.a, ny = c.b;
       const float norm1 = sqrtf((nx + 1) * (ny + 1)) * kOneOverTwoPi;
-      const float phi = kTwoPi * sx;
-      const float sinPhi0 = sqrtf(nx + 1) * yrt_sinf(phi);
-      const float cosPhi0 = sqrtf(ny + 1) * yrt_cosf(phi);
+      const float sinPhi0 = sqrtf(nx + 1) * sd.y;
+      const float cosPhi0 = sqrtf(ny + 1) * sd.x;
       const float nrm = rsqrtf_(sqrf(sinPhi0) + sqrf(cosPhi0));
       const float sinPhi = sinPhi0 * nrm;
       const float cosPhi = cosPhi0 * nrm;
@@ -550,12 +558,12 @@ __device__ __forceinline__ V3 comp_sample(const Comp c, const GpuMaterial* __res
     }
     case C_MINNAERT: {
       YRT_IF_NOT(C_MINNAERT) break;
-      wi = cosine_hemi_dg(sx, sy, dg, pdf);
+      wi = cosine_hemi_dg(sd, dg, pdf);
       return minnaert_eval(c, wo, dg, wi);
     }
     case C_VELVETY: {
       YRT_IF_NOT(C_VELVETY) break;
-      wi = cosine_hemi_dg(sx, sy, dg, pdf);
+      wi = cosine_hemi_dg(sd, dg, pdf);
       return velvety_eval(c, wo, dg, wi);
     }
     case C_DIEL_TRANS: {  // dielectric.h:82-89 (the sample's eta is dropped)
@@ -588,9 +596,8 @@ __device__ __forceinline__ V3 comp_sample(const Comp c, const GpuMaterial* __res
       if (dot(gwo, dg.Ns) > 0.0f) {
         const float n = c.c;
         const float norm1 = (n + 1) * kOneOverTwoPi;
-        const float phi = kTwoPi * sx;
-        const float cosPhi = yrt_cosf(phi);
-        const float sinPhi = yrt_sinf(phi);
+        const float cosPhi = sd.x;
+        const float sinPhi = sd.y;
         const float cosTheta = yrt_powf(sy, rcpf_(n + 1));
         const float sinTheta = cos2sin(cosTheta);
         const V3 wh = mul(dg_F(dg), v3(cosPhi * sinTheta, sinPhi * sinTheta, cosTheta));
@@ -615,10 +622,9 @@ __device__ __forceinline__ V3 comp_sample(const Comp c, const GpuMaterial* __res
       YRT_IF_NOT(C_SPECULAR) break;
       // powerCosineSampleHemisphere(s.x, s.y, reflect(wo, Ns), exp) (shapesampler.h:104-121)
       const float e = c.a;
-      const float phi = kTwoPi * sx;
       const float cosTheta = yrt_powf(sy, rcpf_(e + 1));
       const float sinTheta = cos2sin(cosTheta);
-      V3 l = v3(yrt_cosf(phi) * sinTheta, yrt_sinf(phi) * sinTheta, cosTheta);
+      V3 l = v3(sd.x * sinTheta, sd.y * sinTheta, cosTheta);
       pdf = (e + 1.0f) * yrt_powf(cosTheta, e) * kOneOverTwoPi;
       wi = mul(frame(reflect2(wo, dg.Ns)), l);
       return specular_eval(c, wo, dg, wi);
@@ -651,7 +657,7 @@ __device__ __forceinline__ V3 set_eval(const BRDFSet& bs, const GpuMaterial* __r
 // read back (117 instead of 124 VGPRs: k_shade -3.8 %, C3 +0.9 %, profiles/r02/shade_prune_r02.txt).
 template <unsigned CM>
 __device__ __forceinline__ V3 set_sample(const BRDFSet& bs, const GpuMaterial* __restrict__ mats, V3 wo,
-                                            const DG& dg, float sx, float sy, float ss, V3& wi_o, float& pdf_o,
+                                            const DG& dg, float4 sd, float sy, float ss, V3& wi_o, float& pdf_o,
                                             uint32_t& type_o, float* __restrict__ st) {
   float f[YRT_MAX_COMPS];
   bool ok[YRT_MAX_COMPS];
@@ -665,7 +671,7 @@ __device__ __forceinline__ V3 set_sample(const BRDFSet& bs, const GpuMaterial* _
       V3 wi;
       float pdf = 0.0f;
       const Comp ci = bs.c[i];
-      const V3 c = comp_sample<CM>(ci, mats, wo, dg, sx, sy, wi, pdf);
+      const V3 c = comp_sample<CM>(ci, mats, wo, dg, sd, sy, wi, pdf);
       if (!((c.x == 0.0f && c.y == 0.0f && c.z == 0.0f) || pdf <= 0.0f)) {
         ok[i] = true;
         f[i] = (c.x + c.y + c.z) * rcpf_(pdf);

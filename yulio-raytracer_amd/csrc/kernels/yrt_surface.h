@@ -379,12 +379,18 @@ __device__ __forceinline__ V3 env_Le(const SceneView& sv, const LT& lt, V3 wo) {
   return v3s(0.f);
 }
 
-// Light::sample for a non-precomputed light; returns L, sets wi/pdf.
+// the light types whose sample() reads the raw 2-D sample (sx, sy), and those that read its
+// tabulated terms sd (the point, spot and directional lights read neither)
+constexpr unsigned kLightsRawS = (1u << LIGHT_TRIANGLE) | (1u << LIGHT_DISTANT);
+constexpr unsigned kLightsDir = (1u << LIGHT_AMBIENT) | (1u << LIGHT_DISTANT);
+// Light::sample for a non-precomputed light at the 2-D sample (sx, sy), sd = sample_dir(sx, sy);
+// returns L, sets wi/pdf.
 template <unsigned LM, class LT>
-__device__ __forceinline__ V3 light_sample(const LT& lt, const DG& dg, float sx, float sy, V3& wi, float& pdf) {
+__device__ __forceinline__ V3 light_sample(const LT& lt, const DG& dg, float4 sd, float sx, float sy, V3& wi,
+                                           float& pdf) {
   if ((LM & (1u << LIGHT_AMBIENT)) && lt.type == LIGHT_AMBIENT) {
     // lights/ambientlight.h:52-65 (the bsphere tMax is overwritten by the integrator)
-    wi = cosine_hemi_dg(sx, sy, dg, pdf);
+    wi = cosine_hemi_dg(sd, dg, pdf);
     return v3(lt.L[0], lt.L[1], lt.L[2]);
   }
   if ((LM & (1u << LIGHT_TRIANGLE)) && lt.type == LIGHT_TRIANGLE) {
@@ -428,10 +434,9 @@ __device__ __forceinline__ V3 light_sample(const LT& lt, const DG& dg, float sx,
   }
   if ((LM & (1u << LIGHT_DISTANT)) && lt.type == LIGHT_DISTANT) {  // distantlight.h:46-50, uniformSampleCone (shapesampler.h:149-165)
     const float angle = lt.bsphere[0];
-    const float phi = kTwoPi * sx;
     const float cosTheta = 1.0f - sy * (1.0f - yrt_cosf(angle));
     const float sinTheta = cos2sin(cosTheta);
-    const V3 l = v3(yrt_cosf(phi) * sinTheta, yrt_sinf(phi) * sinTheta, cosTheta);
+    const V3 l = v3(sd.x * sinTheta, sd.y * sinTheta, cosTheta);
     pdf = rcpf_(4.0f * kPi * sqrf(yrt_sinf(0.5f * angle)));
     wi = mul(frame(ld3(lt.e1)), l);
     return v3(lt.L[0], lt.L[1], lt.L[2]);

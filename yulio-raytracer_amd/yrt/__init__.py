@@ -245,6 +245,32 @@ class Device:
                                      out.ctypes.data), "yrtDebugShade")
         return out
 
+    def debug_sample_dirs(self, spp, sets, iteration, num1D, num2D, filter="bspline"):
+        """yrtDebugSampleDirs: the request's frame cache entry as a render creates it. Returns its
+        sample table, float32 (dims, records), and its direction-term table read back from the
+        device, float32 (num2D, records, 4)."""
+        n = N.dev.yrtDebugSampleDirs(self.h, spp, sets, iteration, num1D, num2D, _b(filter), None, 0, None, 0)
+        if n < 0:
+            raise RuntimeError(f"yrtDebugSampleDirs: {self.error()}")
+        dims = np.zeros((5 + num1D + 2 * num2D, n), np.float32)
+        dirs = np.zeros((num2D, n, 4), np.float32)
+        if N.dev.yrtDebugSampleDirs(self.h, spp, sets, iteration, num1D, num2D, _b(filter),
+                                    dims.ctypes.data_as(N.PF), dims.size, dirs.ctypes.data_as(N.PF), dirs.size) != n:
+            raise RuntimeError(f"yrtDebugSampleDirs: {self.error()}")
+        return dims, dirs
+
+    def debug_dir_terms(self, mode, u, v):
+        """yrtDebugDirTerms: (cosPhi, sinPhi, cosTheta, sinTheta) of the samples (u[i], v[i]), float32
+        (n, 4). mode 0: the probe kernel that spells them out; mode 1: the table's own kernel."""
+        u = np.ascontiguousarray(u, np.float32).ravel()
+        v = np.ascontiguousarray(v, np.float32).ravel()
+        if u.size != v.size:
+            raise ValueError("one v per u")
+        out = np.zeros((u.size, 4), np.float32)
+        self._rc(N.dev.yrtDebugDirTerms(self.h, int(mode), u.ctypes.data_as(N.PF), v.ctypes.data_as(N.PF), u.size,
+                                        out.ctypes.data_as(N.PF)), "yrtDebugDirTerms")
+        return out
+
     # -- rendering (device.h:223-234)
     def rtRenderFrame(self, renderer, camera, scene, toneMapper, frameBuffer, accumulate=0):
         self._rc(N.dev.yrtRenderFrame(self.h, renderer, camera, scene, toneMapper, frameBuffer, int(accumulate)),

@@ -193,6 +193,11 @@ try:  # the shading-layer probe; absent from older builds selected with YRT_LIB_
     _sig(dev, "yrtDebugShade", i32, vp, i32, vp, vp, i32, vp, i32, vp)
 except AttributeError:
     pass
+try:  # the direction-term table's probes; absent from older builds selected with YRT_LIB_DIR
+    _sig(dev, "yrtDebugSampleDirs", i32, vp, i32, i32, i32, i32, i32, cstr, PF, sz, PF, sz)
+    _sig(dev, "yrtDebugDirTerms", i32, vp, i32, PF, PF, i32, PF)
+except AttributeError:
+    pass
 try:  # the denoise stage; absent from older builds selected with YRT_LIB_DIR
     _sig(dev, "yrtRenderGuides", i32, vp, vp, vp, i32, i32, vp, vp)
     _sig(dev, "yrtDenoiseDefaults", i32, C.POINTER(DenoiseParams))
