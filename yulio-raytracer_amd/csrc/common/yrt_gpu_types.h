@@ -50,11 +50,11 @@ struct GpuTriMotion {
 };
 static_assert(sizeof(GpuTriMotion) == 64, "moving tri record size");
 
-// Per triangle (global id order): what k_shade's postIntersect reads of a static mesh triangle,
-// in one 96-byte record instead of an index record plus nine vertex gathers (positions,
-// normals, texcoords): e1 = p0 - p1, e2 = p2 - p0 (the geometric normal's edges; p1 - p0 is
-// -e1 bit for bit), the vertex normals and texture coordinates (zero where the mesh has
-// none), and the geometry id. Moving meshes and meshes with tangent arrays keep the indexed path.
+// Per triangle (global id order): what postIntersect's record source (TriRecordSource,
+// kernels/yrt_surface.h: k_shade, k_guides) reads of a static mesh triangle, 96 bytes for an index
+// record plus nine vertex gathers: e1 = p0 - p1, e2 = p2 - p0 (yrt_tri_record.h; -e1 is p1 - p0
+// but for a zero's sign, -0 for +0), the vertex normals and texcoords (zero where the mesh has
+// none), and the geometry id. Moving meshes and meshes with tangent arrays: the indexed source.
 struct GpuTriShade {
   float e1[3];
   int32_t geom;

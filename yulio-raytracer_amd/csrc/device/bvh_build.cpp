@@ -17,6 +17,8 @@
 #include <algorithm>
 #include <stdexcept>
 
+#include "../common/yrt_tri_record.h"
+
 namespace yrt {
 
 namespace {
@@ -582,10 +584,7 @@ void build_bvh(const std::vector<float>& v /* 9 floats per triangle */, const st
     const int id = leafIds[i];
     const float* t = &v[(size_t)id * 9];
     GpuTri& g = out.tris[i];
-    // e1 = v0 - v1, e2 = v2 - v0 (rtcore convention)
-    g.v0[0] = t[0]; g.v0[1] = t[1]; g.v0[2] = t[2];
-    g.e1[0] = t[0] - t[3]; g.e1[1] = t[1] - t[4]; g.e1[2] = t[2] - t[5];
-    g.e2[0] = t[6] - t[0]; g.e2[1] = t[7] - t[1]; g.e2[2] = t[8] - t[2];
+    yrt_tri_vertices(g, t, t + 3, t + 6);
     int gid = id;
     uint32_t fl = flags[id];
     memcpy(&g.v0[3], &gid, 4);

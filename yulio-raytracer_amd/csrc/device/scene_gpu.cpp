@@ -11,6 +11,7 @@
 #include <chrono>
 #include <map>
 
+#include "../common/yrt_tri_record.h"
 #include "bvh_build.h"
 #include "distribution.h"
 
@@ -351,18 +352,14 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
     for (size_t t = 0; t < indices.size(); ++t) {
       const int4 ix = indices[t];
       const int v[3] = {ix.x, ix.y, ix.z};
-      GpuTriShade& r = ts[t];
-      memset(&r, 0, sizeof(r));
-      const float4 p0 = positions[ix.x], p1 = positions[ix.y], p2 = positions[ix.z];
-      r.e1[0] = p0.x - p1.x; r.e1[1] = p0.y - p1.y; r.e1[2] = p0.z - p1.z;
-      r.e2[0] = p2.x - p0.x; r.e2[1] = p2.y - p0.y; r.e2[2] = p2.z - p0.z;
-      r.geom = ix.w;
+      float p[3][3], n[3][3], st[3][2];
       for (int k = 0; k < 3; ++k) {
-        const float4 n = normals[v[k]];
-        r.n[3 * k] = n.x; r.n[3 * k + 1] = n.y; r.n[3 * k + 2] = n.z;
-        r.st[2 * k] = texcoords[v[k]].x;
-        r.st[2 * k + 1] = texcoords[v[k]].y;
+        const float4 pk = positions[v[k]], nk = normals[v[k]];
+        p[k][0] = pk.x; p[k][1] = pk.y; p[k][2] = pk.z;
+        n[k][0] = nk.x; n[k][1] = nk.y; n[k][2] = nk.z;
+        st[k][0] = texcoords[v[k]].x; st[k][1] = texcoords[v[k]].y;
       }
+      yrt_tri_shade_fill(ts[t], p[0], p[1], p[2], n[0], n[1], n[2], st[0], st[1], st[2], ix.w);
     }
     S->triShade.upload(ts);
   }

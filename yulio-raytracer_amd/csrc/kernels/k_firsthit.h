@@ -1,5 +1,5 @@
 // k_firsthit.h — the first-hit kernels off the render loop, the three callers of closest_hit
-// (yrt_traverse.h): the debug renderer, rtPick and the denoiser's guide pass.
+// (yrt_traverse.h): the debug renderer, rtPick and the guide pass (k_shade's post_intersect).
 #pragma once
 
 #include "yrt_camera.h"
@@ -48,8 +48,9 @@ __global__ __launch_bounds__(64) void k_debug(SceneView sv, FrameView fv, int ma
           if (depth + 1 < maxDepth) {
             const int4 idx = sv.indices[h.tri];
             const V3 p0 = ld3(sv.positions[idx.x]), p1 = ld3(sv.positions[idx.y]), p2 = ld3(sv.positions[idx.z]);
-            const V3 Ng = cross(p0 - p1, p2 - p0);  // ray.Ng
-            V3 Nf = normalize(Ng);
+            V3 e1, e2;
+            yrt_tri_edges(&p0.x, &p1.x, &p2.x, &e1.x, &e2.x);
+            V3 Nf = normalize(cross(e1, e2));  // ray.Ng
             if (dot(-dir, Nf) < 0) Nf = -Nf;
             const float u1 = rnd.getFloat();
             const float u2 = rnd.getFloat();
@@ -126,8 +127,10 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) void k_guides(SceneView sv, const 
     return;
   }
   DG dg;
-  const int g = sv.triGeom[h.tri];
-  post_intersect_g(sv, sv.geoms[g], org, dir, h.t, h.u, h.v, h.tri, dg, false);
+  const float4* tsr = (const float4*)(sv.triShade + h.tri);
+  const float4 r0 = tsr[0];
+  const int g = __float_as_int(r0.w);  // geometry id rides in the shading record
+  post_intersect(sv, sv.geoms[g], tsr, r0, org, dir, h.t, h.u, h.v, h.tri, dg, false, 0.f);
   V3 n = dg.Ns;
   if (dot(n, dir) > 0.f) n = -n;
   pos4[i] = make_float4(dg.P.x, dg.P.y, dg.P.z, h.t);

@@ -5,6 +5,7 @@
 #include "yrt_wave.h"
 #include "../common/yrt_gpu_types.h"
 #include "../common/yrt_qnode.h"
+#include "../common/yrt_tri_record.h"
 
 namespace yrt {
 
@@ -27,22 +28,11 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_refit_tris(GpuTri* __restrict__ t
   const int gid = firstTri + i;
   const int4 ix = indices[gid];
   const float4 a = positions[ix.x], b = positions[ix.y], c = positions[ix.z];
-  // the shading record's edges and vertex normals (scene_gpu.cpp builds it the same way)
-  GpuTriShade& ts = triShade[gid];
-  ts.e1[0] = a.x - b.x; ts.e1[1] = a.y - b.y; ts.e1[2] = a.z - b.z;
-  ts.e2[0] = c.x - a.x; ts.e2[1] = c.y - a.y; ts.e2[2] = c.z - a.z;
   const float4 na = normals[ix.x], nb = normals[ix.y], nc = normals[ix.z];
-  ts.n[0] = na.x; ts.n[1] = na.y; ts.n[2] = na.z;
-  ts.n[3] = nb.x; ts.n[4] = nb.y; ts.n[5] = nb.z;
-  ts.n[6] = nc.x; ts.n[7] = nc.y; ts.n[8] = nc.z;
-  // every leaf slot referencing the triangle (spatial splits duplicate references)
-  for (int k = leafStart[gid]; k < leafStart[gid + 1]; ++k) {
-    GpuTri& t = tris[leafSlots[k]];
-    // e1 = v0 - v1, e2 = v2 - v0 (device/bvh_build.cpp, rtcore convention); .w words kept
-    t.v0[0] = a.x; t.v0[1] = a.y; t.v0[2] = a.z;
-    t.e1[0] = a.x - b.x; t.e1[1] = a.y - b.y; t.e1[2] = a.z - b.z;
-    t.e2[0] = c.x - a.x; t.e2[1] = c.y - a.y; t.e2[2] = c.z - a.z;
-  }
+  // the host builder's functions: the shading record's edges and vertex normals (st, geom stay), and
+  // every leaf slot referencing the triangle (spatial splits duplicate references; .w words kept)
+  yrt_tri_shade_vertices(triShade[gid], &a.x, &b.x, &c.x, &na.x, &nb.x, &nc.x);
+  for (int k = leafStart[gid]; k < leafStart[gid + 1]; ++k) yrt_tri_vertices(tris[leafSlots[k]], &a.x, &b.x, &c.x);
 }
 
 __global__ __launch_bounds__(YRT_BLOCK) void k_refit_nodes(GpuNode* __restrict__ nodes, const GpuTri* __restrict__ tris,

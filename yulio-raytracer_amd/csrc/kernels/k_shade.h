@@ -169,8 +169,7 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
       // tangents only feed the Obj bump map and the anisotropic microfacet
       const bool wantT = mat >= 0 && (((MM & mat_bit(MAT_OBJ)) && gr.m.type == MAT_OBJ && gr.m.tex[4] >= 0) ||
                                       ((MM & mat_bit(MAT_BRUSHED_METAL)) && gr.m.type == MAT_BRUSHED_METAL));
-      post_intersect_rec(sv, gr.g, tsr, r0, org, dir, h.x, h.y, h.z, gid, dg, wantT,
-                         pb.qTime[0] ? samp(fv, 4, rec) : 0.f);
+      post_intersect(sv, gr.g, tsr, r0, org, dir, h.x, h.y, h.z, gid, dg, wantT, pb.qTime[0] ? samp(fv, 4, rec) : 0.f);
       if (dot(dg.Ng, dir) > 0.f) {
         backfacing = true;
         dg.Ng = -dg.Ng;

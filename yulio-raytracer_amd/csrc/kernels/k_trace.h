@@ -4,6 +4,7 @@
 
 #include "yrt_camera.h"
 #include "yrt_traverse.h"
+#include "../common/yrt_tri_record.h"
 
 namespace yrt {
 
@@ -91,12 +92,11 @@ __device__ __forceinline__ GpuTri tri_at(const GpuTri* __restrict__ tris, const 
   GpuTri t = tris[slot];
   if constexpr (MOTION) {
     const GpuTriMotion m = tms[slot];
-    const float p0x = t.v0[0] + time * m.m0[0], p0y = t.v0[1] + time * m.m0[1], p0z = t.v0[2] + time * m.m0[2];
-    const float p1x = m.p1[0] + time * m.m1[0], p1y = m.p1[1] + time * m.m1[1], p1z = m.p1[2] + time * m.m1[2];
-    const float p2x = m.p2[0] + time * m.m2[0], p2y = m.p2[1] + time * m.m2[1], p2z = m.p2[2] + time * m.m2[2];
-    t.v0[0] = p0x; t.v0[1] = p0y; t.v0[2] = p0z;
-    t.e1[0] = p0x - p1x; t.e1[1] = p0y - p1y; t.e1[2] = p0z - p1z;
-    t.e2[0] = p2x - p0x; t.e2[1] = p2y - p0y; t.e2[2] = p2z - p0z;
+    float p0[3], p1[3], p2[3];
+    for (int k = 0; k < 3; ++k) p0[k] = t.v0[k] + time * m.m0[k];
+    for (int k = 0; k < 3; ++k) p1[k] = m.p1[k] + time * m.m1[k];
+    for (int k = 0; k < 3; ++k) p2[k] = m.p2[k] + time * m.m2[k];
+    yrt_tri_vertices(t, p0, p1, p2);
   }
   return t;
 }

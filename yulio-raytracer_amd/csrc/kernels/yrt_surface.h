@@ -5,162 +5,125 @@
 
 #include "yrt_shade.h"
 #include "yrt_wave.h"
+#include "../common/yrt_tri_record.h"
 
 namespace yrt {
 
-// ---------------------------------------------------------------- shading helpers
-// BackendSceneFlat::postIntersect -> Shape::postIntersect
-// geom: the hit triangle's geometry record (sv.geoms / the geometry part of sv.geomRecs)
-// time: the ray's time (moving geometry, GF_MOTION: vertices p + time * m, trianglemesh_full.cpp:211-215)
-__device__ __forceinline__ void post_intersect_g(const SceneView& sv, const GpuGeom& geom, V3 org, V3 dir, float t,
-                                                 float u, float v, int gid, DG& dg, bool wantTangents,
-                                                 float time = 0.f) {
+// ---------------------------------------------------------------- postIntersect
+// BackendSceneFlat::postIntersect -> Shape::postIntersect, written once (post_intersect) over two
+// vertex sources, which answer for a mesh triangle's edges, vertex normals, texture coordinates and
+// interpolated tangents. A source loads inside its accessor: only what the mesh's flags ask for.
+
+// Record source: the triangle's 96-byte GpuTriShade (rec), r0 = its first 16 bytes, which the
+// caller has loaded for the geometry id. Static meshes without tangent arrays.
+struct TriRecordSource {
+  static constexpr bool kTangentArrays = false;
+  const float4* __restrict__ rec;
+  float4 r0;
+  __device__ __forceinline__ void edges(V3& e1, V3& e2, V3& dPdu, V3& dPdv) const {
+    const float4 r1 = rec[1];
+    e1 = v3(r0.x, r0.y, r0.z); e2 = v3(r1.x, r1.y, r1.z);
+    dPdu = -e1; dPdv = e2;  // p1 - p0 but for a zero's sign: -0 where the indexed source has +0
+  }
+  __device__ __forceinline__ void normals(V3& n0, V3& n1, V3& n2) const {
+    const float4 r2 = rec[2], r3 = rec[3], r4 = rec[4];
+    n0 = v3(r2.x, r2.y, r2.z); n1 = v3(r2.w, r3.x, r3.y); n2 = v3(r3.z, r3.w, r4.x);
+  }
+  __device__ __forceinline__ void texcoords(float2& st0, float2& st1, float2& st2) const {
+    const float4 r4 = rec[4], r5 = rec[5];
+    st0 = make_float2(r4.y, r4.z); st1 = make_float2(r4.w, r5.x); st2 = make_float2(r5.y, r5.z);
+  }
+};
+
+// Indexed source: the index record and the vertex arrays, for moving meshes (GF_MOTION: vertices
+// p + time * m, trianglemesh_full.cpp:211-215) and meshes with tangent arrays (tangent k: 0 Tx, 1 Ty).
+struct TriIndexedSource {
+  static constexpr bool kTangentArrays = true;
+  const SceneView& sv;
+  const int4 idx;
+  const float time;
+  const bool moving;
+  __device__ __forceinline__ void edges(V3& e1, V3& e2, V3& dPdu, V3& dPdv) const {
+    V3 p0 = ld3(sv.positions[idx.x]), p1 = ld3(sv.positions[idx.y]), p2 = ld3(sv.positions[idx.z]);
+    if (moving) {
+      p0 = p0 + time * ld3(sv.motions[idx.x]);
+      p1 = p1 + time * ld3(sv.motions[idx.y]);
+      p2 = p2 + time * ld3(sv.motions[idx.z]);
+    }
+    yrt_tri_edges(&p0.x, &p1.x, &p2.x, &e1.x, &e2.x);  // the record writers' (common/yrt_tri_record.h)
+    dPdu = p1 - p0; dPdv = p2 - p0;
+  }
+  __device__ __forceinline__ void normals(V3& n0, V3& n1, V3& n2) const {
+    n0 = ld3(sv.normals[idx.x]); n1 = ld3(sv.normals[idx.y]); n2 = ld3(sv.normals[idx.z]);
+  }
+  __device__ __forceinline__ void texcoords(float2& st0, float2& st1, float2& st2) const {
+    st0 = sv.texcoords[idx.x]; st1 = sv.texcoords[idx.y]; st2 = sv.texcoords[idx.z];
+  }
+  __device__ __forceinline__ V3 tangent(int k, float w, float u, float v) const {
+    return w * ld3(sv.tangents[2 * idx.x + k]) + u * ld3(sv.tangents[2 * idx.y + k]) +
+           v * ld3(sv.tangents[2 * idx.z + k]);
+  }
+};
+
+// geom: the hit triangle's geometry record; rec: its GpuTriShade, r0 = rec[0] (already loaded
+// for the geometry id); (u, v): the hit's barycentrics; time: the ray's time.
+__device__ __forceinline__ void post_intersect(const SceneView& sv, const GpuGeom& geom,
+                                               const float4* __restrict__ rec, float4 r0, V3 org, V3 dir, float t,
+                                               float u, float v, int gid, DG& dg, bool wantTangents, float time) {
   dg.material = geom.material;
   dg.light = geom.light;
   dg.illumMask = geom.illumMask;
   dg.shadowMask = geom.shadowMask;
   dg.P = org + t * dir;
-  if (geom.kind == GEOM_TRIANGLE) {
-    // shapes/triangle.h:69-78
-    dg.Ng = v3(geom.Ng[0], geom.Ng[1], geom.Ng[2]);
-    dg.Ns = dg.Ng;
-    dg.s = u;
-    dg.t = v;
-    dg.Tx = dg.Ty = v3s(0.f);
-  } else {
-    const int4 idx = sv.indices[gid];
-    V3 p0 = ld3(sv.positions[idx.x]), p1 = ld3(sv.positions[idx.y]), p2 = ld3(sv.positions[idx.z]);
-    if (geom.flags & GF_MOTION) {
-      p0 = p0 + time * ld3(sv.motions[idx.x]);
-      p1 = p1 + time * ld3(sv.motions[idx.y]);
-      p2 = p2 + time * ld3(sv.motions[idx.z]);
-    }
+  dg.s = u; dg.t = v;  // unless the mesh has texture coordinates
+  dg.Tx = dg.Ty = v3s(0.f);
+  auto mesh = [&](const auto src) {  // TriangleMeshFull / TriangleMeshWithNormals::postIntersect
+    V3 e1, e2, dPdu, dPdv;
+    src.edges(e1, e2, dPdu, dPdv);
     const float w = 1.0f - u - v;
-    const V3 dPdu = p1 - p0, dPdv = p2 - p0;
-    dg.Ng = normalize(cross(p0 - p1, p2 - p0));  // ray.Ng (unnormalized Embree Ng)
-    if (geom.kind == GEOM_MESH_NORMALS) {
-      // shapes/trianglemesh_normals.cpp:125-147
-      dg.s = u;
-      dg.t = v;
-      const V3 n0 = ld3(sv.normals[idx.x]), n1 = ld3(sv.normals[idx.y]), n2 = ld3(sv.normals[idx.z]);
+    dg.Ns = dg.Ng = normalize(cross(e1, e2));  // ray.Ng (unnormalized Embree Ng)
+    const bool meshNormals = geom.kind == GEOM_MESH_NORMALS;
+    if (meshNormals || (geom.flags & GF_NORMALS)) {
+      V3 n0, n1, n2;
+      src.normals(n0, n1, n2);
       V3 Ns = w * n0 + u * n1 + v * n2;
       const float len2 = dot(Ns, Ns);
       Ns = len2 > 0 ? Ns * rsqrtf_(len2) : dg.Ng;
       if (dot(Ns, dg.Ng) < 0) Ns = -Ns;
       dg.Ns = Ns;
-      dg.Tx = dPdu;
-      dg.Ty = dPdv;
-    } else {
-      // shapes/trianglemesh_full.cpp:192-260
-      float dsdu, dtdu, dsdv, dtdv;
-      if (geom.flags & GF_TEXCOORDS) {
-        const float2 st0 = sv.texcoords[idx.x], st1 = sv.texcoords[idx.y], st2 = sv.texcoords[idx.z];
-        dg.s = st0.x * w + st1.x * u + st2.x * v;
-        dg.t = st0.y * w + st1.y * u + st2.y * v;
-        dsdu = st1.x - st0.x; dtdu = st1.y - st0.y;
-        dsdv = st2.x - st0.x; dtdv = st2.y - st0.y;
-      } else {
-        dg.s = u;
-        dg.t = v;
-        dsdu = 1; dtdu = 0;
-        dsdv = 0; dtdv = 1;
-      }
-      if (geom.flags & GF_NORMALS) {
-        const V3 n0 = ld3(sv.normals[idx.x]), n1 = ld3(sv.normals[idx.y]), n2 = ld3(sv.normals[idx.z]);
-        V3 Ns = w * n0 + u * n1 + v * n2;
-        const float len2 = dot(Ns, Ns);
-        Ns = len2 > 0 ? Ns * rsqrtf_(len2) : dg.Ng;
-        if (dot(Ns, dg.Ng) < 0) Ns = -Ns;
-        dg.Ns = Ns;
-      } else {
-        dg.Ns = dg.Ng;
-      }
-      if (wantTangents) {
-        // trianglemesh_full.cpp:244-263: interpolated tangents when the mesh has them
-        if (geom.flags & GF_TANGENT_X) {
-          dg.Tx = w * ld3(sv.tangents[2 * idx.x]) + u * ld3(sv.tangents[2 * idx.y]) + v * ld3(sv.tangents[2 * idx.z]);
-        } else {
-          const V3 dPds = normalize(dPdu * dtdv - dPdv * dtdu);
-          dg.Tx = normalize(dPds - dot(dPds, dg.Ns) * dg.Ns);
-        }
-        if (geom.flags & GF_TANGENT_Y) {
-          dg.Ty = w * ld3(sv.tangents[2 * idx.x + 1]) + u * ld3(sv.tangents[2 * idx.y + 1]) +
-                  v * ld3(sv.tangents[2 * idx.z + 1]);
-        } else {
-          const V3 dPdt = normalize(dPdv * dsdu - dPdu * dsdv);
-          dg.Ty = normalize(dPdt - dot(dPdt, dg.Ns) * dg.Ns);
-        }
-      } else {
-        dg.Tx = dg.Ty = v3s(0.f);
-      }
     }
-  }
-  dg.error = fmaxf(fabsf(t), reduce_max(absv(dg.P)));
-}
-// k_shade's postIntersect: static mesh triangles read their GpuTriShade record (r0 = its
-// first 16 bytes, already loaded for the geometry id) instead of the index record and the
-// vertex arrays; the same operations as post_intersect_g on the same values, so the same bits.
-// Single triangles, moving meshes and meshes with tangent arrays take post_intersect_g.
-__device__ __forceinline__ void post_intersect_rec(const SceneView& sv, const GpuGeom& geom,
-                                                   const float4* __restrict__ rec, float4 r0, V3 org, V3 dir, float t,
-                                                   float u, float v, int gid, DG& dg, bool wantTangents, float time) {
-  if (geom.kind == GEOM_TRIANGLE || (geom.flags & (GF_MOTION | GF_TANGENT_X | GF_TANGENT_Y))) {
-    post_intersect_g(sv, geom, org, dir, t, u, v, gid, dg, wantTangents, time);
-    return;
-  }
-  dg.material = geom.material;
-  dg.light = geom.light;
-  dg.illumMask = geom.illumMask;
-  dg.shadowMask = geom.shadowMask;
-  dg.P = org + t * dir;
-  const float4 r1 = rec[1];
-  const V3 e1 = v3(r0.x, r0.y, r0.z), e2 = v3(r1.x, r1.y, r1.z);  // p0 - p1, p2 - p0
-  const float w = 1.0f - u - v;
-  const V3 dPdu = -e1, dPdv = e2;  // p1 - p0 (negation is exact), p2 - p0
-  dg.Ng = normalize(cross(e1, e2));
-  const bool meshNormals = geom.kind == GEOM_MESH_NORMALS;
-  if (meshNormals || (geom.flags & GF_NORMALS)) {
-    const float4 r2 = rec[2], r3 = rec[3], r4 = rec[4];
-    const V3 n0 = v3(r2.x, r2.y, r2.z), n1 = v3(r2.w, r3.x, r3.y), n2 = v3(r3.z, r3.w, r4.x);
-    V3 Ns = w * n0 + u * n1 + v * n2;
-    const float len2 = dot(Ns, Ns);
-    Ns = len2 > 0 ? Ns * rsqrtf_(len2) : dg.Ng;
-    if (dot(Ns, dg.Ng) < 0) Ns = -Ns;
-    dg.Ns = Ns;
-  } else {
-    dg.Ns = dg.Ng;
-  }
-  if (meshNormals) {
-    // shapes/trianglemesh_normals.cpp:125-147
-    dg.s = u;
-    dg.t = v;
-    dg.Tx = dPdu;
-    dg.Ty = dPdv;
-  } else {
+    if (meshNormals) {  // shapes/trianglemesh_normals.cpp:125-147
+      dg.Tx = dPdu; dg.Ty = dPdv;
+      return;
+    }
     // shapes/trianglemesh_full.cpp:192-260
-    float dsdu, dtdu, dsdv, dtdv;
+    float dsdu = 1, dtdu = 0, dsdv = 0, dtdv = 1;
     if (geom.flags & GF_TEXCOORDS) {
-      const float4 r4 = rec[4], r5 = rec[5];
-      const float2 st0 = make_float2(r4.y, r4.z), st1 = make_float2(r4.w, r5.x), st2 = make_float2(r5.y, r5.z);
+      float2 st0, st1, st2;
+      src.texcoords(st0, st1, st2);
       dg.s = st0.x * w + st1.x * u + st2.x * v;
       dg.t = st0.y * w + st1.y * u + st2.y * v;
       dsdu = st1.x - st0.x; dtdu = st1.y - st0.y;
       dsdv = st2.x - st0.x; dtdv = st2.y - st0.y;
-    } else {
-      dg.s = u;
-      dg.t = v;
-      dsdu = 1; dtdu = 0;
-      dsdv = 0; dtdv = 1;
     }
-    if (wantTangents) {
-      const V3 dPds = normalize(dPdu * dtdv - dPdv * dtdu);
-      dg.Tx = normalize(dPds - dot(dPds, dg.Ns) * dg.Ns);
-      const V3 dPdt = normalize(dPdv * dsdu - dPdu * dsdv);
-      dg.Ty = normalize(dPdt - dot(dPdt, dg.Ns) * dg.Ns);
-    } else {
-      dg.Tx = dg.Ty = v3s(0.f);
+    if (!wantTangents) return;
+    // trianglemesh_full.cpp:244-263: derived tangents, interpolated ones where the mesh has them
+    const V3 dPds = normalize(dPdu * dtdv - dPdv * dtdu);
+    dg.Tx = normalize(dPds - dot(dPds, dg.Ns) * dg.Ns);
+    const V3 dPdt = normalize(dPdv * dsdu - dPdu * dsdv);
+    dg.Ty = normalize(dPdt - dot(dPdt, dg.Ns) * dg.Ns);
+    if constexpr (src.kTangentArrays) {
+      if (geom.flags & GF_TANGENT_X) dg.Tx = src.tangent(0, w, u, v);
+      if (geom.flags & GF_TANGENT_Y) dg.Ty = src.tangent(1, w, u, v);
     }
-  }
+  };
+  // the one place that picks the source: the vertex arrays for moving meshes and tangent arrays
+  if (geom.kind == GEOM_TRIANGLE)  // shapes/triangle.h:69-78
+    dg.Ns = dg.Ng = v3(geom.Ng[0], geom.Ng[1], geom.Ng[2]);
+  else if (geom.flags & (GF_MOTION | GF_TANGENT_X | GF_TANGENT_Y))
+    mesh(TriIndexedSource{sv, sv.indices[gid], time, (geom.flags & GF_MOTION) != 0});
+  else
+    mesh(TriRecordSource{rec, r0});
   dg.error = fmaxf(fabsf(t), reduce_max(absv(dg.P)));
 }
 
