@@ -130,7 +130,8 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) void k_guides(SceneView sv, const 
   const float4* tsr = (const float4*)(sv.triShade + h.tri);
   const float4 r0 = tsr[0];
   const int g = __float_as_int(r0.w);  // geometry id rides in the shading record
-  post_intersect(sv, sv.geoms[g], tsr, r0, org, dir, h.t, h.u, h.v, h.tri, dg, false, 0.f);
+  // the lazy record source: one pixel per thread, once per frame; the burst would only add registers
+  post_intersect(sv, sv.geoms[g], TriRecordLazySource{tsr, r0}, org, dir, h.t, h.u, h.v, h.tri, dg, false, 0.f);
   V3 n = dg.Ns;
   if (dot(n, dir) > 0.f) n = -n;
   pos4[i] = make_float4(dg.P.x, dg.P.y, dg.P.z, h.t);

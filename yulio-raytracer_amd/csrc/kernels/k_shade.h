@@ -20,6 +20,31 @@ namespace yrt {
 #ifndef YRT_SHADE_WAVES_MP
 #define YRT_SHADE_WAVES_MP YRT_SHADE_WAVES  // instantiations with MetallicPaint (C4's set)
 #endif
+// A hit vertex's loads in groups (profiles/shade_bursts_ab.txt), each switched off
+// with -D...=0 and chosen per instantiation by the traits below:
+//   YRT_SHADE_BURST_REC    the 96-byte GpuTriShade record in one group of six loads beside its
+//                          first piece (TriRecordSource), before the geometry record is known
+//   YRT_SHADE_BURST_GEOM   the geometry record's fields in one group (geom_burst)
+//   YRT_SHADE_STORES_LAST  the continuation's and the first light's queue reservations together
+//                          with no store in flight, the records' stores and pathL after them
+#ifndef YRT_SHADE_BURST_REC
+#define YRT_SHADE_BURST_REC 1
+#endif
+#ifndef YRT_SHADE_BURST_GEOM
+#define YRT_SHADE_BURST_GEOM 1
+#endif
+#ifndef YRT_SHADE_STORES_LAST
+#define YRT_SHADE_STORES_LAST 1
+#endif
+template <unsigned MM>
+constexpr bool shade_burst_rec() { return YRT_SHADE_BURST_REC != 0; }
+template <unsigned MM>
+constexpr bool shade_burst_geom() { return YRT_SHADE_BURST_GEOM != 0; }
+// not with MetallicPaint (C4's set): the continuation record kept live across the first light's
+// term spills there (8 B of scratch at 128 VGPRs)
+template <unsigned MM>
+constexpr bool shade_stores_last() { return YRT_SHADE_STORES_LAST != 0 && !(MM & mat_bit(MAT_METALLIC_PAINT)); }
+
 #ifdef YRT_PATH_DEBUG
 // Debug builds only (-DYRT_PATH_DEBUG): per-vertex record of one path (pixel id, sample) of the
 // shade kernel, 32 floats per depth, laid out as oracle_debug_path's (tools/c5_path_debug.py).
@@ -156,20 +181,49 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
     SPROF_MARK(1);  // misses: environment / backplate
     bool backfacing = false;
     int g = 0;  // the hit's geometry (sv.geomRecs)
+    // the geometry record's material and tex[0] descriptor in registers (geom_burst)
+    GpuMaterial gm = {};
+    GpuTexture gt0 = {};
     if (active && isHit) {
       const int gid = __float_as_int(h.w);
       const float4* tsr = (const float4*)(sv.triShade + gid);
-      const float4 r0 = tsr[0];
+      // The whole record beside its first piece: the five other addresses are known with the hit,
+      // the geometry record (which says what of it the mesh reads) only after r[0]. In bounds for
+      // every hit: a hit's id is a global triangle id, and triShade holds one full 96-byte record
+      // per global triangle id, whatever its geometry's kind (scene_gpu.cpp sizes it by the index
+      // array, which spheres, disks and `triangle` shapes are tessellated into); r[0] is read for
+      // every hit already. GEOM_TRIANGLE and the indexed source ignore the other 80 bytes.
+      TriRecordSource trs;
+      trs.r[0] = tsr[0];
+      if constexpr (shade_burst_rec<MM>()) {
+#pragma unroll
+        for (int k = 1; k < 6; ++k) trs.r[k] = tsr[k];
+      }
+      const float4 r0 = trs.r[0];
       const float4 o = pb.qOrg[cur][q];
       org = v3(o.x, o.y, o.z);
       rec = fv.pixelSets[pixelId] * rp.spp + s;
       g = __float_as_int(r0.w);  // geometry id rides in the shading record
-      const GpuGeomRec& gr = sv.geomRecs[g];
-      const int mat = gr.g.material;
+      const float time = pb.qTime[0] ? samp(fv, 4, rec) : 0.f;
       // tangents only feed the Obj bump map and the anisotropic microfacet
-      const bool wantT = mat >= 0 && (((MM & mat_bit(MAT_OBJ)) && gr.m.type == MAT_OBJ && gr.m.tex[4] >= 0) ||
-                                      ((MM & mat_bit(MAT_BRUSHED_METAL)) && gr.m.type == MAT_BRUSHED_METAL));
-      post_intersect(sv, gr.g, tsr, r0, org, dir, h.x, h.y, h.z, gid, dg, wantT, pb.qTime[0] ? samp(fv, 4, rec) : 0.f);
+      auto want_tangents = [&](int mat, const GpuMaterial& m) {
+        return mat >= 0 && (((MM & mat_bit(MAT_OBJ)) && m.type == MAT_OBJ && m.tex[4] >= 0) ||
+                            ((MM & mat_bit(MAT_BRUSHED_METAL)) && m.type == MAT_BRUSHED_METAL));
+      };
+      auto post = [&](const auto& geom, bool wantT) {
+        if constexpr (shade_burst_rec<MM>())
+          post_intersect(sv, geom, trs, org, dir, h.x, h.y, h.z, gid, dg, wantT, time);
+        else
+          post_intersect(sv, geom, TriRecordLazySource{tsr, r0}, org, dir, h.x, h.y, h.z, gid, dg, wantT, time);
+      };
+      if constexpr (shade_burst_geom<MM>()) {
+        GeomHead gh;
+        geom_burst<MM>(sv.geomRecs + g, gh, gm, gt0);
+        post(gh, want_tangents(gh.material, gm));
+      } else {
+        const GpuGeomRec& gr = sv.geomRecs[g];
+        post(gr.g, want_tangents(gr.g.material, gr.m));
+      }
       if (dot(dg.Ng, dir) > 0.f) {
         backfacing = true;
         dg.Ng = -dg.Ng;
@@ -178,7 +232,10 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
     }
     SPROF_MARK(2);  // postIntersect
     if (active && isHit) {
-      if (dg.material >= 0) shade_material<MM>(sv, sv.geomRecs[g].m, sv.geomRecs[g].t0, dg.material, medium, dg, bs);
+      if (dg.material >= 0) {
+        if constexpr (shade_burst_geom<MM>()) shade_material<MM>(sv, gm, gt0, dg.material, medium, dg, bs);
+        else shade_material<MM>(sv, sv.geomRecs[g].m, sv.geomRecs[g].t0, dg.material, medium, dg, bs);
+      }
       if (!ignoreVL && dg.light >= 0 && !backfacing) {
         const GpuLight& al = sv.lights[dg.light];
         if (!haveL) { const float4 l4 = pb.pathL[path]; L = v3(l4.x, l4.y, l4.z); haveL = true; }
@@ -248,7 +305,11 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
       }
     }
     SPROF_MARK(4);  // continuation: CompositedBRDF::sample, Russian roulette
-    if (haveL) pb.pathL[path] = make_float4(L.x, L.y, L.z, 0.f);
+    // pathL[path]: nothing in this kernel reads it after this point, so where it is stored is
+    // free. A store counts in the same counter as the loads and the atomics' returns: stored
+    // here, the continuation's reservation below waits for its acknowledgement as well.
+    if constexpr (!shade_stores_last<MM>())
+      if (haveL) pb.pathL[path] = make_float4(L.x, L.y, L.z, 0.f);
     // the continuation's records (pathtraceintegrator.cpp:169-213) at queue slot nq
     auto cont_store = [&](unsigned nq) {
       if (pb.qTime[0]) pb.qTime[cur ^ 1][nq] = samp(fv, 4, rec);  // lastRay.time (:210)
@@ -310,7 +371,41 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
       pb.sDir[si] = make_float4(wi.x, wi.y, wi.z, tfar);
       pb.sContrib[si] = make_float4(contrib.x, contrib.y, contrib.z, __int_as_float(path));
     };
-    {
+    auto shadow_append = [&](int k, bool pred, const V3& wi, float tfar, const V3& contrib) {
+      bool sgot;
+      const unsigned si = oseg * pb.shSegCap + wave_append(shadowCount, pred, sgot);
+      if (sgot) shadow_store(si, wi, tfar, contrib);
+      if (active && !pb.fuseShadow) pb.shFirst[(size_t)q * numDirect + k] = sgot ? (int)si : -1;
+    };
+    if constexpr (shade_stores_last<MM>()) {
+      // The first light's term is worked out before either reservation (it stores nothing), the
+      // two reservations go out together with no store in flight, and every store of the vertex
+      // follows them: a slot is written only after its reservation has returned, as before. The
+      // continuation record stays live across the first light's term.
+      V3 wi = v3s(0.f), contrib = v3s(0.f);
+      float tfar = 0.f;
+      const bool pred = numDirect > 0 && light_term(0, wi, tfar, contrib);
+      SPROF_FINE(5);
+      unsigned nq, si;
+      wave_append2(nextCount, cont, nq, shadowCount, pred, si);
+      nq += oseg * pb.segCap;
+      si += oseg * pb.shSegCap;
+      if (cont) cont_store(nq);
+      SPROF_MARK(5);
+      SPROF_FINE(2);
+      if (numDirect > 0) {
+        if (pred) shadow_store(si, wi, tfar, contrib);
+        if (active && !pb.fuseShadow) pb.shFirst[(size_t)q * numDirect] = pred ? (int)si : -1;
+      }
+      SPROF_FINE(6);
+      for (int k = 1; k < numDirect; ++k) {
+        const bool predk = light_term(k, wi, tfar, contrib);
+        SPROF_FINE(5);
+        shadow_append(k, predk, wi, tfar, contrib);
+        SPROF_FINE(6);
+      }
+      if (haveL) pb.pathL[path] = make_float4(L.x, L.y, L.z, 0.f);
+    } else {
       bool got;
       const unsigned nq = oseg * pb.segCap + wave_append(nextCount, cont, got);
       if (got) cont_store(nq);
@@ -321,10 +416,7 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
         float tfar = 0.f;
         const bool pred = light_term(k, wi, tfar, contrib);
         SPROF_FINE(5);  // shadow-ray jitter, contribution
-        bool sgot;
-        const unsigned si = oseg * pb.shSegCap + wave_append(shadowCount, pred, sgot);
-        if (sgot) shadow_store(si, wi, tfar, contrib);
-        if (active && !pb.fuseShadow) pb.shFirst[(size_t)q * numDirect + k] = sgot ? (int)si : -1;
+        shadow_append(k, pred, wi, tfar, contrib);
         SPROF_FINE(6);  // shadow-ray append and stores
       }
     }

@@ -12,18 +12,38 @@ namespace yrt {
 // ---------------------------------------------------------------- postIntersect
 // BackendSceneFlat::postIntersect -> Shape::postIntersect, written once (post_intersect) over two
 // vertex sources, which answer for a mesh triangle's edges, vertex normals, texture coordinates and
-// interpolated tangents. A source loads inside its accessor: only what the mesh's flags ask for.
+// interpolated tangents. The lazy and the indexed source load inside their accessors: only what
+// the mesh's flags ask for. The burst source holds the whole record in registers.
 
-// Record source: the triangle's 96-byte GpuTriShade (rec), r0 = its first 16 bytes, which the
-// caller has loaded for the geometry id. Static meshes without tangent arrays.
+// Record source: the triangle's 96-byte GpuTriShade, static meshes without tangent arrays. Its
+// six 16-byte pieces r[0..5], all loaded by the caller (k_shade: in one group beside r[0], before
+// the geometry record is known, so that a hit waits for its record once and not four times).
 struct TriRecordSource {
+  static constexpr bool kTangentArrays = false;
+  float4 r[6];
+  __device__ __forceinline__ void edges(V3& e1, V3& e2, V3& dPdu, V3& dPdv) const {
+    e1 = v3(r[0].x, r[0].y, r[0].z); e2 = v3(r[1].x, r[1].y, r[1].z);
+    dPdu = -e1; dPdv = e2;  // p1 - p0 but for a zero's sign: -0 where the indexed source has +0
+  }
+  __device__ __forceinline__ void normals(V3& n0, V3& n1, V3& n2) const {
+    n0 = v3(r[2].x, r[2].y, r[2].z); n1 = v3(r[2].w, r[3].x, r[3].y); n2 = v3(r[3].z, r[3].w, r[4].x);
+  }
+  __device__ __forceinline__ void texcoords(float2& st0, float2& st1, float2& st2) const {
+    st0 = make_float2(r[4].y, r[4].z); st1 = make_float2(r[4].w, r[5].x); st2 = make_float2(r[5].y, r[5].z);
+  }
+};
+
+// The same record read piece by piece inside the accessors (rec), r0 = its first 16 bytes, which
+// the caller has loaded for the geometry id: k_guides, off the render loop, and k_shade
+// instantiations built without the record burst.
+struct TriRecordLazySource {
   static constexpr bool kTangentArrays = false;
   const float4* __restrict__ rec;
   float4 r0;
   __device__ __forceinline__ void edges(V3& e1, V3& e2, V3& dPdu, V3& dPdv) const {
     const float4 r1 = rec[1];
     e1 = v3(r0.x, r0.y, r0.z); e2 = v3(r1.x, r1.y, r1.z);
-    dPdu = -e1; dPdv = e2;  // p1 - p0 but for a zero's sign: -0 where the indexed source has +0
+    dPdu = -e1; dPdv = e2;
   }
   __device__ __forceinline__ void normals(V3& n0, V3& n1, V3& n2) const {
     const float4 r2 = rec[2], r3 = rec[3], r4 = rec[4];
@@ -65,11 +85,20 @@ struct TriIndexedSource {
   }
 };
 
-// geom: the hit triangle's geometry record; rec: its GpuTriShade, r0 = rec[0] (already loaded
-// for the geometry id); (u, v): the hit's barycentrics; time: the ray's time.
-__device__ __forceinline__ void post_intersect(const SceneView& sv, const GpuGeom& geom,
-                                               const float4* __restrict__ rec, float4 r0, V3 org, V3 dir, float t,
-                                               float u, float v, int gid, DG& dg, bool wantTangents, float time) {
+// The fields of a GpuGeom that post_intersect reads, held in registers (geom_burst below); Ng
+// stays in memory, read by GEOM_TRIANGLE hits only.
+struct GeomHead {
+  int32_t kind, material, light, flags, illumMask, shadowMask;
+  const float* Ng;
+};
+
+// geom: the hit triangle's geometry record (a GpuGeom or a GeomHead); rec: the record source of
+// its GpuTriShade (TriRecordSource or TriRecordLazySource); (u, v): the hit's barycentrics; time:
+// the ray's time.
+template <class GEOM, class REC>
+__device__ __forceinline__ void post_intersect(const SceneView& sv, const GEOM& geom, const REC& rec, V3 org, V3 dir,
+                                               float t, float u, float v, int gid, DG& dg, bool wantTangents,
+                                               float time) {
   dg.material = geom.material;
   dg.light = geom.light;
   dg.illumMask = geom.illumMask;
@@ -123,8 +152,64 @@ __device__ __forceinline__ void post_intersect(const SceneView& sv, const GpuGeo
   else if (geom.flags & (GF_MOTION | GF_TANGENT_X | GF_TANGENT_Y))
     mesh(TriIndexedSource{sv, sv.indices[gid], time, (geom.flags & GF_MOTION) != 0});
   else
-    mesh(TriRecordSource{rec, r0});
+    mesh(rec);
   dg.error = fmaxf(fabsf(t), reduce_max(absv(dg.P)));
+}
+
+// ---------------------------------------------------------------- the geometry record in one group
+// What an instantiation's shade_material cases and post_intersect read of a hit's GpuGeomRec,
+// issued as 16-byte loads in one group when the geometry id is known: the record is 13 such
+// pieces (q), all inside the one record, and shade_material then selects among registers in
+// place of loading a field, waiting, branching on it and loading the next.
+//   q0 q1   GpuGeom: kind, material, light, flags | vtxBase, triBase, illumMask, shadowMask
+//   q2      GpuGeom::Ng (GEOM_TRIANGLE only: left in memory)
+//   q3      m.type, m.tex[0..2]        q4  m.tex[3..4], m.media[0..1]
+//   q5..q10 m.p[0..23]                 q11 q12  t0
+// number of leading p[] pieces the material types of MM read (the cases of shade_material)
+template <unsigned MM>
+constexpr int mat_p_quads() {
+  int n = 0;
+  constexpr unsigned one = mat_bit(MAT_MATTE) | mat_bit(MAT_MIRROR) | mat_bit(MAT_MATTE_TEXTURED);            // p[0..3]
+  constexpr unsigned two = mat_bit(MAT_VELVET) | mat_bit(MAT_OBJ) | mat_bit(MAT_METALLIC_PAINT);             // p[0..7]
+  constexpr unsigned three = mat_bit(MAT_PLASTIC) | mat_bit(MAT_DIELECTRIC) | mat_bit(MAT_METAL) |
+                             mat_bit(MAT_METALLIC_GLITTER) | mat_bit(MAT_UBER) | mat_bit(MAT_THIN_DIELECTRIC);  // p[0..11]
+  constexpr unsigned four = mat_bit(MAT_BRUSHED_METAL);                                                       // p[0..12]
+  if (MM & one) n = 1;
+  if (MM & two) n = 2;
+  if (MM & three) n = 3;
+  if (MM & four) n = 4;
+  return n;
+}
+// the material types that read tex[3..4] or media[] (q4), and those that sample tex[0] through t0
+constexpr unsigned kMatsQ4 = mat_bit(MAT_OBJ) | mat_bit(MAT_DIELECTRIC);
+constexpr unsigned kMatsT0 = mat_bit(MAT_MATTE_TEXTURED) | mat_bit(MAT_OBJ) | mat_bit(MAT_UBER) | mat_bit(MAT_THIN_DIELECTRIC);
+
+// m and t0 are written only where MM's materials read them; the rest keeps the caller's zeros.
+template <unsigned MM>
+__device__ __forceinline__ void geom_burst(const GpuGeomRec* __restrict__ gr, GeomHead& gh, GpuMaterial& m,
+                                           GpuTexture& t0) {
+  static_assert(sizeof(GpuGeom) == 48 && sizeof(GpuMaterial) == 128 && sizeof(GpuGeomRec) == 208, "piece offsets below");
+  const int4* __restrict__ q = (const int4*)gr;
+  constexpr int NP = mat_p_quads<MM>();
+  const int4 q0 = q[0], q1 = q[1], q3 = q[3];
+  int4 q4 = make_int4(0, 0, 0, 0), qt0 = q4, qt1 = q4;
+  float4 qp[4];
+  if constexpr ((MM & kMatsQ4) != 0u) q4 = q[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) qp[k] = k < NP ? ((const float4*)gr)[5 + k] : make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr ((MM & kMatsT0) != 0u) { qt0 = q[11]; qt1 = q[12]; }
+  gh.kind = q0.x; gh.material = q0.y; gh.light = q0.z; gh.flags = q0.w;
+  gh.illumMask = q1.z; gh.shadowMask = q1.w;
+  gh.Ng = gr->g.Ng;
+  m.type = q3.x; m.tex[0] = q3.y; m.tex[1] = q3.z; m.tex[2] = q3.w;
+  if constexpr ((MM & kMatsQ4) != 0u) { m.tex[3] = q4.x; m.tex[4] = q4.y; m.media[0] = q4.z; m.media[1] = q4.w; }
+#pragma unroll
+  for (int k = 0; k < NP; ++k) { m.p[4 * k] = qp[k].x; m.p[4 * k + 1] = qp[k].y; m.p[4 * k + 2] = qp[k].z; m.p[4 * k + 3] = qp[k].w; }
+  if constexpr ((MM & kMatsT0) != 0u) {
+    t0.image = qt0.x; t0.filter = qt0.y; t0.invert = qt0.z; t0.width = qt0.w;
+    t0.height = qt1.x; t0.format = qt1.y;
+    t0.offset = (int64_t)(((uint64_t)(uint32_t)qt1.w << 32) | (uint32_t)qt1.z);
+  }
 }
 
 __device__ __forceinline__ void add_comp(BRDFSet& bs, int kind, uint32_t type, V3 R, float a = 0.f, float b = 0.f,

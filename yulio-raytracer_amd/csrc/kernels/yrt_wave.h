@@ -43,6 +43,34 @@ __device__ __forceinline__ unsigned wave_append(unsigned* counter, bool pred, bo
   return base + (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
 }
 
+// Two appends at once: one lane issues both atomics back to back, so the wave waits for the
+// slower of the two round trips and not for their sum. Slots as two wave_append calls give them.
+__device__ __forceinline__ void wave_append2(unsigned* counter0, bool pred0, unsigned& slot0, unsigned* counter1,
+                                             bool pred1, unsigned& slot1) {
+  const unsigned long long m0 = ballot(pred0), m1 = ballot(pred1);
+  slot0 = slot1 = 0;
+  if ((m0 | m1) == 0) return;
+  const int lane = lane_id();
+  const int leader = __ffsll((long long)(m0 | m1)) - 1;
+  unsigned b0 = 0, b1 = 0;
+  if (lane == leader) {
+    // wave-uniform cases, so that a counter nobody appends to sees no atomic
+    if (m0 != 0 && m1 != 0) {
+      b0 = atomicAdd(counter0, (unsigned)__popcll(m0));
+      b1 = atomicAdd(counter1, (unsigned)__popcll(m1));
+    } else if (m0 != 0) {
+      b0 = atomicAdd(counter0, (unsigned)__popcll(m0));
+    } else {
+      b1 = atomicAdd(counter1, (unsigned)__popcll(m1));
+    }
+  }
+  b0 = __shfl(b0, leader, 64);
+  b1 = __shfl(b1, leader, 64);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  slot0 = b0 + (unsigned)__popcll(m0 & below);
+  slot1 = b1 + (unsigned)__popcll(m1 & below);
+}
+
 // ---------------------------------------------------------------- segmented queues
 struct QMap {
   unsigned pre[YRT_QSEGS + 1];  // exclusive prefix of the segment counts; pre[numSegs] = total
