@@ -248,6 +248,32 @@ typedef struct YRTSceneInfo {
   int64_t nodeBytesClosest, nodeBytesAny;
 } YRTSceneInfo;
 YRT_API int yrtGetSceneInfo(YRTDevice dev, YRTHandle scene, YRTSceneInfo* out);
+/* The scene builder. yrtSetString(scene, "builder", "morton") before yrtCommit builds the BVH on
+ * the GPU: 63-bit Morton keys of the triangles' box centres, a stable radix sort, Karras' radix
+ * tree with leaves of up to 8 triangles, collapsed to the same 4-wide nodes (on a "host" device
+ * the same steps run in a serial loop and give the same tree). "default" and every other value
+ * keep the host's binned-SAH builder; the environment variable YRT_BUILDER=morton makes "default"
+ * mean "morton". Hits and frames do not depend on the builder, only the time to build and to
+ * traverse. A commit that asks for another builder than the tree's rebuilds; vertex-only commits
+ * after a morton build refit as after any other.
+ * yrtGetSceneBuildInfo: the BVH step of the scene's last build (not of a refit). size = the bytes
+ * of the caller's struct, set by the caller; nothing is written past it.
+ *   builder   0 host SAH, 1 morton on the GPU, 2 morton's host loop
+ *   fallback  why a morton commit used the host SAH builder after all: 0 it did not, 1 fewer than
+ *             2 triangles, 2 a vertex that is not finite, 3 the traversal stack bound would exceed
+ *             the kernels' stack, 4 node or reference limits
+ *   msBuild   wall time of the BVH step alone, upload and download of a GPU build included
+ *             (YRTSceneInfo::buildSeconds is the whole commit)
+ *   msKernels HIP-event time of the build kernels with yrtSetKernelTiming on, else 0
+ *   sahCost   over every child box of the float nodes: area(child) / area(root) x (1 for an inner
+ *             child, the triangle count for a leaf) */
+typedef struct YRTSceneBuildInfo {
+  uint32_t size;
+  int32_t builder, fallback;
+  int32_t pad;
+  double msBuild, msKernels, sahCost;
+} YRTSceneBuildInfo;
+YRT_API int yrtGetSceneBuildInfo(YRTDevice dev, YRTHandle scene, YRTSceneBuildInfo* out);
 /* Copies the host mirror of the BVH (4-wide nodes: 128 B each, numTriRefs leaf tris: 48 B each). */
 YRT_API int yrtExportBVH(YRTDevice dev, YRTHandle scene, void* nodes, size_t nodesBytes, void* tris,
                          size_t trisBytes);

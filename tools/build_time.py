@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""Where a scene commit's time goes, and what the scene builder "morton" costs and saves
+(DESIGN.md §10): per scene and builder, in one process and in alternating order,
+
+  commit     YRTSceneInfo::buildSeconds, the whole commit (flatten, BVH, quantize, upload, tables)
+  bvh        YRTSceneBuildInfo::msBuild, the BVH step alone (a GPU build's upload/download included)
+  kernels    YRTSceneBuildInfo::msKernels, HIP-event time of the build kernels
+  sahCost, nodes, bvhDepth
+  visits     node / triangle visits per ray of incoherent rays through the quantized nodes in the
+             kernel's order (oracle.count_visits; a CPU number), with --visits
+  frame      wall time of a path-traced frame (C3: the view; C5: cube face 0), with --frames N
+
+    python tools/build_time.py [--host] [--scenes C3,C5,HF20] [--reps 3] [--visits] [--frames 5]
+
+Scenes: C3 (yrt.standin), C5 (yrt.frederick), HFn (a 2^n-triangle height field). --host runs the
+builders' host paths on the host-only device (morton's serial loop, builder 2).
+"""
+from __future__ import annotations
+
+import argparse
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (ROOT, ROOT / "yulio-raytracer_amd", ROOT / "tests"):
+    sys.path.insert(0, str(p))
+
+import oracle  # noqa: E402
+import yrt  # noqa: E402
+
+BUILDERS = ("default", "morton")
+
+
+def session_args(which, size, spp):
+    if which == "C3":
+        from yrt import standin
+        return ["-i", str(standin.write_xml())] + standin.C3_ARGS + ["-size", str(size), str(size), "-spp", str(spp)], -1
+    from yrt import frederick
+    return ["-fprCollada", "-i", str(frederick.write_dae()), "-stereo", "-size", str(size), str(size), "-spp", str(spp)], 0
+
+
+def height_field(n_tris, seed=41):
+    """A jittered height field of n_tris triangles (vectorised)."""
+    nx = int(np.ceil(np.sqrt(n_tris / 2)))
+    nz = int(np.ceil(n_tris / (2 * nx)))
+    rng = np.random.default_rng(seed)
+    x, z = np.meshgrid(np.arange(nx + 1.0), np.arange(nz + 1.0))
+    n = x.size
+    pos = np.stack([x.ravel() + rng.uniform(-0.3, 0.3, n), rng.uniform(0.0, 1.5, n),
+                    z.ravel() + rng.uniform(-0.3, 0.3, n)], 1).astype(np.float32)
+    j, i = np.meshgrid(np.arange(nz), np.arange(nx), indexing="ij")
+    a = (j * (nx + 1) + i).ravel()
+    b, c, d = a + 1, a + nx + 2, a + nx + 1
+    idx = np.stack([np.stack([a, b, c], 1), np.stack([a, c, d], 1)], 1).reshape(-1, 3).astype(np.int32)
+    return pos, np.ascontiguousarray(idx[:n_tris])
+
+
+def incoherent(tri9, n, seed=42):
+    v = tri9.reshape(-1, 3)
+    lo, hi = v.min(0), v.max(0)
+    rng = np.random.default_rng(seed)
+    org = rng.uniform(lo, hi, size=(n, 3))
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return (np.concatenate([org, np.zeros((n, 1))], 1).astype(np.float32),
+            np.concatenate([d, np.full((n, 1), np.inf)], 1).astype(np.float32))
+
+
+def measure(dev, which, builder, a):
+    """One commit of the scene with the builder; returns the row and an object to render with."""
+    if which.startswith("HF"):
+        import trace_scenes as ts
+        pos, idx = height_field(1 << int(which[2:]))
+        S = ts.MeshScene.__new__(ts.MeshScene)   # the mesh in a scene of its own, committed once
+        S.dev = dev
+        S.mat = dev.rtNewMaterial("Matte")
+        dev.rtCommit(S.mat)
+        S.scene = dev.rtNewScene("default")
+        S.meshes = [{"idx": idx, "cull": False}]
+        S._set_mesh(0, pos, None)
+        dev.rtSetString(S.scene, "builder", builder)
+        dev.rtCommit(S.scene)
+        scene, sess, face = S.scene, None, None
+        tri9 = pos[idx].reshape(-1, 9)
+    else:
+        args, face = session_args(which, a.size, a.spp)
+        sess = yrt.Session(args + ["-builder", builder, "-fb", "RGB_FLOAT32"], device=dev)
+        scene = sess.info()["scene"]
+        tri9 = None
+    info, bi = dev.scene_info(scene), dev.scene_build_info(scene)
+    row = {"commit": info["buildSeconds"] * 1e3, "bvh": bi["msBuild"], "kernels": bi["msKernels"],
+           "sahCost": bi["sahCost"], "nodes": info["numNodes"], "bvhDepth": info["bvhDepth"],
+           "tris": info["numTriangles"], "builder": bi["builder"], "fallback": bi["fallback"]}
+    if a.visits:
+        if tri9 is None:
+            tri9 = oracle.scene_triangles(sess.export_frame())
+        org, dr = incoherent(tri9, a.rays)
+        nodes, tris = dev.export_bvh(scene)
+        nv, tv, _ = oracle.count_visits(nodes, tris, org, dr, tri_bytes=info["triRecordBytes"],
+                                        qnodes=dev.export_qbvh(scene))
+        row["nodeVisits"], row["triVisits"] = nv / a.rays, tv / a.rays
+    return row, sess, face
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--scenes", default="C3,C5,HF20")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--visits", action="store_true")
+    ap.add_argument("--rays", type=int, default=4096)
+    ap.add_argument("--frames", type=int, default=0)
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--spp", type=int, default=8)
+    a = ap.parse_args()
+    dev = yrt.Device(host=True) if a.host else yrt.Device(0)
+    if not a.host:
+        dev.set_kernel_timing(True)
+    for which in a.scenes.split(","):
+        rows = {b: [] for b in BUILDERS}
+        frames = {b: [] for b in BUILDERS}
+        for rep in range(a.reps):
+            for b in (BUILDERS if rep % 2 == 0 else BUILDERS[::-1]):
+                row, sess, face = measure(dev, which, b, a)
+                rows[b].append(row)
+                if sess is not None and a.frames and not a.host:
+                    sess.render(face, read=False)          # warm-up: sample tables, allocations
+                    for _ in range(a.frames):
+                        t0 = time.perf_counter()
+                        sess.render(face, read=False)
+                        frames[b].append((time.perf_counter() - t0) * 1e3)
+                if sess is not None:
+                    sess.close()
+        for b in BUILDERS:
+            r = rows[b]
+            med = lambda k: statistics.median(x[k] for x in r)  # noqa: E731
+            line = (f"{which:5s} {b:8s} tris {r[0]['tris']:8d} builder {r[0]['builder']} fallback {r[0]['fallback']} "
+                    f"commit {med('commit'):9.2f} ms  bvh {med('bvh'):9.2f} ms (min {min(x['bvh'] for x in r):.2f} "
+                    f"max {max(x['bvh'] for x in r):.2f})  kernels {med('kernels'):7.3f} ms  "
+                    f"sahCost {r[0]['sahCost']:.3f} nodes {r[0]['nodes']} bvhDepth {r[0]['bvhDepth']}")
+            if a.visits:
+                line += f"  visits/ray node {r[0]['nodeVisits']:.2f} tri {r[0]['triVisits']:.2f}"
+            if frames[b]:
+                f = frames[b]
+                line += (f"  frame {a.size}^2 {a.spp} spp: median {statistics.median(f):.2f} ms min {min(f):.2f} "
+                         f"max {max(f):.2f} (n {len(f)})")
+            print(line, flush=True)
+    dev.close()
+
+
+if __name__ == "__main__":
+    main()

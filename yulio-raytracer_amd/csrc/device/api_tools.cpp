@@ -49,6 +49,24 @@ int yrtGetSceneInfo(YRTDevice dev, YRTHandle scene, YRTSceneInfo* out) {
   return 0;
   DEV_END(-1)
 }
+int yrtGetSceneBuildInfo(YRTDevice dev, YRTHandle scene, YRTSceneBuildInfo* out) {
+  DEV_GUARD(dev, -1)
+  auto S = dev->d->get<SceneObj>(scene, "scene");
+  if (!S->gpu) throw std::runtime_error("scene not committed");
+  if (!out || out->size < sizeof(out->size)) throw std::runtime_error("yrtGetSceneBuildInfo: size not set");
+  const BuildInfo& b = S->gpu->buildInfo;
+  YRTSceneBuildInfo r;
+  memset(&r, 0, sizeof(r));
+  r.size = out->size;
+  r.builder = b.builder;
+  r.fallback = b.fallback;
+  r.msBuild = b.msBuild;
+  r.msKernels = b.msKernels;
+  r.sahCost = b.sahCost;
+  memcpy(out, &r, std::min((size_t)out->size, sizeof(r)));  // never past the caller's struct
+  return 0;
+  DEV_END(-1)
+}
 int yrtExportBVH(YRTDevice dev, YRTHandle scene, void* nodes, size_t nodesBytes, void* tris, size_t trisBytes) {
   DEV_GUARD(dev, -1)
   auto S = dev->d->get<SceneObj>(scene, "scene");

@@ -15,8 +15,10 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <stdexcept>
 
+#include "../common/yrt_lbvh.h"
 #include "../common/yrt_tri_record.h"
 
 namespace yrt {
@@ -591,6 +593,130 @@ void build_bvh(const std::vector<float>& v /* 9 floats per triangle */, const st
     memcpy(&g.e1[3], &fl, 4);
     g.e2[3] = 0.f;
   }
+}
+
+// ---------------------------------------------------------------- scene builder "morton", host loop
+// The steps of common/yrt_lbvh.h over every element in turn, in the order in which
+// kernels/bvh_build.hip launches them; the "host" device builds with this loop (builder 2), and
+// the GPU tests require the kernels to give its bytes.
+int build_bvh_morton_host(const std::vector<float>& v, const std::vector<uint32_t>& flags, int stackDepth,
+                          BvhResult& out, const std::vector<float>* v1) {
+  const size_t N64 = v.size() / 9;
+  if (N64 < 2) return FALLBACK_FEW_TRIANGLES;
+  if (N64 >= (size_t(1) << 26)) return FALLBACK_SIZE;
+  const int N = (int)N64;
+  // 1 boxes, centroid bounds
+  std::vector<LbvhBox> box(N);
+  LbvhBox cb;
+  lbvh_box_reset(cb);
+  bool finite = true;
+  for (int i = 0; i < N; ++i) {
+    finite = lbvh_prim_box(&v[(size_t)i * 9], v1 ? &(*v1)[(size_t)i * 9] : nullptr, box[i]) && finite;
+    LbvhBox c;
+    for (int k = 0; k < 3; ++k) c.lo[k] = c.hi[k] = lbvh_centroid(box[i], k);
+    lbvh_box_grow(cb, c);
+  }
+  if (!finite) return FALLBACK_NON_FINITE;
+  // 2 keys, stable sort
+  std::vector<uint64_t> key(N), keys(N);
+  std::vector<uint32_t> slotId(N);
+  for (int i = 0; i < N; ++i) { key[i] = lbvh_key(box[i], cb); slotId[i] = (uint32_t)i; }
+  std::stable_sort(slotId.begin(), slotId.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+  for (int i = 0; i < N; ++i) keys[i] = key[slotId[i]];
+  // 3, 4 hierarchy, leaves, levels
+  std::vector<LbvhNode2> nodes2(N - 1);
+  std::vector<int> parent(N - 1, -1);
+  std::vector<char> inner(N - 1, 0);
+  for (int i = 0; i < N - 1; ++i) {
+    int first, last, split;
+    lbvh_range(keys.data(), N, i, first, last, split);
+    if (!lbvh_is_inner(i, first, last)) continue;
+    inner[i] = 1;
+    lbvh_node2(first, last, split, nodes2[i]);
+    for (int c = 0; c < 2; ++c)
+      if (nodes2[i].cnt[c] == 0) parent[nodes2[i].idx[c]] = i;
+  }
+  std::vector<std::vector<int>> levels;
+  for (int i = 0; i < N - 1; ++i) {
+    if (!inner[i]) continue;
+    int d = 0;
+    for (int p = parent[i]; p >= 0; p = parent[p]) ++d;
+    if (d >= YRT_LBVH_MAX_LEVELS) return FALLBACK_STACK;
+    if ((int)levels.size() <= d) levels.resize(d + 1);
+    levels[d].push_back(i);
+  }
+  // 5 boxes, deepest level first
+  for (int d = (int)levels.size() - 1; d >= 0; --d)
+    for (int i : levels[d])
+      for (int c = 0; c < 2; ++c) {
+        LbvhBox b;
+        lbvh_child_box(nodes2.data(), box.data(), slotId.data(), i, c, b);
+        nodes2[i].b[c] = b;
+      }
+  // 6 - 8 collapse, one 4-wide level at a time; numbered by an exclusive scan over the level
+  std::vector<GpuNode> nodes;
+  std::vector<int> frontier = {0}, stackAbove = {0}, next, nextStack, off;
+  int maxStack = 0;
+  for (int level = 0; !frontier.empty(); ++level) {
+    if (level >= YRT_LBVH_MAX_LEVELS) return FALLBACK_STACK;
+    const size_t base = nodes.size(), cnt = frontier.size();
+    if (base + cnt >= (size_t(1) << 25)) return FALLBACK_SIZE;
+    off.assign(cnt, 0);
+    int total = 0;
+    LbvhRef ch[4];
+    for (size_t f = 0; f < cnt; ++f) {
+      off[f] = total;
+      total += lbvh_count_inner(ch, lbvh_collapse(nodes2.data(), frontier[f], ch));
+    }
+    nodes.resize(base + cnt);
+    next.assign(total, 0);
+    nextStack.assign(total, 0);
+    for (size_t f = 0; f < cnt; ++f) {
+      const int k = lbvh_collapse(nodes2.data(), frontier[f], ch);
+      const int stackHere = stackAbove[f] + (k - 1);
+      maxStack = std::max(maxStack, stackHere);
+      int nx[4];
+      lbvh_emit(nodes[base + f], ch, k, (int)(base + cnt) + off[f], nx);
+      for (int r = 0; r < lbvh_count_inner(ch, k); ++r) { next[off[f] + r] = nx[r]; nextStack[off[f] + r] = stackHere; }
+    }
+    frontier.swap(next);
+    stackAbove.swap(nextStack);
+  }
+  if (maxStack > stackDepth - 1) return FALLBACK_STACK;
+  // 9 leaf records: sorted order is leaf order
+  out.maxDepth = maxStack;
+  out.nodes = std::move(nodes);
+  out.order.assign(slotId.begin(), slotId.end());
+  out.tris.resize(N);
+  for (int i = 0; i < N; ++i) lbvh_leaf_record(out.tris[i], v.data(), flags.data(), slotId[i]);
+  return FALLBACK_NONE;
+}
+
+double bvh_sah_cost(const std::vector<GpuNode>& nodes) {
+  if (nodes.empty()) return 0;
+  auto area = [](const GpuNode& n, int j) {
+    const double dx = (double)n.hix[j] - n.lox[j], dy = (double)n.hiy[j] - n.loy[j], dz = (double)n.hiz[j] - n.loz[j];
+    return dx >= 0 && dy >= 0 && dz >= 0 ? 2.0 * (dx * dy + dy * dz + dz * dx) : 0.0;
+  };
+  LbvhBox root;
+  lbvh_box_reset(root);
+  for (int j = 0; j < 4; ++j) {
+    if (nodes[0].child[j] == -1) continue;
+    const GpuNode& n = nodes[0];
+    const LbvhBox b = {{n.lox[j], n.loy[j], n.loz[j]}, {n.hix[j], n.hiy[j], n.hiz[j]}};
+    lbvh_box_grow(root, b);
+  }
+  const double dx = (double)root.hi[0] - root.lo[0], dy = (double)root.hi[1] - root.lo[1], dz = (double)root.hi[2] - root.lo[2];
+  const double rootArea = 2.0 * (dx * dy + dy * dz + dz * dx);
+  if (!(rootArea > 0) || !std::isfinite(rootArea)) return 0;
+  double cost = 0;
+  for (const GpuNode& n : nodes)
+    for (int j = 0; j < 4; ++j) {
+      const int c = n.child[j];
+      if (c == -1) continue;
+      cost += area(n, j) * ((c & 31) ? (double)(c & 31) : (double)YRT_SAH_TRAV);
+    }
+  return cost / rootArea;
 }
 
 }  // namespace yrt

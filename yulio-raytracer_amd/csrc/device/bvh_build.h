@@ -22,5 +22,37 @@ struct BvhResult {
 void build_bvh(const std::vector<float>& v, const std::vector<uint32_t>& flags, int stackDepth, BvhResult& out,
                const std::vector<float>* v1 = nullptr);
 
+// ---------------------------------------------------------------- scene builder "morton"
+// An LBVH (63-bit Morton keys, Karras 2012) collapsed to the same 4-wide nodes; the steps are in
+// common/yrt_lbvh.h. The result depends on the triangles alone: the serial host loop and the
+// kernels (kernels/bvh_build.hip) give the same bytes on every run. Both take build_bvh's
+// arguments and return 0 with `out` filled, or the reason why the caller has to use build_bvh:
+enum BuildFallback {
+  FALLBACK_NONE = 0,
+  FALLBACK_FEW_TRIANGLES = 1,  // fewer than 2
+  FALLBACK_NON_FINITE = 2,     // a vertex (or a box centre) is not finite
+  FALLBACK_STACK = 3,          // the worst-case traversal stack exceeds stackDepth - 1
+  FALLBACK_SIZE = 4            // node / reference limits of build_bvh
+};
+enum BuilderKind { BUILDER_SAH = 0, BUILDER_MORTON_GPU = 1, BUILDER_MORTON_HOST = 2 };
+int build_bvh_morton_host(const std::vector<float>& v, const std::vector<uint32_t>& flags, int stackDepth,
+                          BvhResult& out, const std::vector<float>* v1 = nullptr);
+// On the current HIP device, in `stream` (a hipStream_t); returns after the tree is downloaded.
+// msKernels (timing only): summed HIP-event time of the build's kernels.
+int build_bvh_morton_gpu(const std::vector<float>& v, const std::vector<uint32_t>& flags, int stackDepth,
+                         BvhResult& out, const std::vector<float>* v1, void* stream, bool timing, double* msKernels);
+
+// What yrtGetSceneBuildInfo reports of a commit's BVH step
+struct BuildInfo {
+  int builder = BUILDER_SAH;
+  int fallback = FALLBACK_NONE;
+  double msBuild = 0;    // wall time of the BVH step alone
+  double msKernels = 0;  // HIP-event time of the build kernels (kernel timing on), else 0
+  double sahCost = 0;
+};
+// sum over all child boxes of area(child) / area(root) * (YRT_SAH_TRAV for an inner child, the
+// triangle count for a leaf); 0 for an empty tree or a root without area
+double bvh_sah_cost(const std::vector<GpuNode>& nodes);
+
 
 }  // namespace yrt

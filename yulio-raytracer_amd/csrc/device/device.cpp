@@ -124,13 +124,24 @@ void Device::intersect(SceneObj& S, const float* org4, const float* dir4, uint32
 void SceneObj::commit() {
   std::vector<std::shared_ptr<ScenePrim>> prims = slots;
   Device* d = static_cast<Device*>(dev);
+  // scene property "builder" (api/scene.h:45): "morton" builds the BVH on the GPU (bvh_build.h),
+  // every other value is the host SAH builder; YRT_BUILDER=morton makes "default" mean "morton"
+  const Variant* bv = parms.find("builder");
+  std::string builder = bv && bv->type == Variant::STRING ? bv->str : "default";
+  if (builder == "default") {
+    const char* env = getenv("YRT_BUILDER");
+    if (env) builder = env;
+  }
+  const bool morton = builder == "morton";
   // per-face commits of the FPR loop (renderer.cpp:550-559) only re-orient faceCamera
-  // meshes: refit on the GPU instead of rebuilding
-  if (gpu && d->gpu && d->refitCommits) {
+  // meshes: refit on the GPU instead of rebuilding; a tree of the other
+  // builder is never refit
+  if (gpu && d->gpu && d->refitCommits && gpu->mortonAsked == morton) {
     HIP_CHECK(hipSetDevice(d->hipDevice));
     if (refit_gpu_scene(*gpu, prims, d->stream)) return;
   }
-  gpu = build_gpu_scene(prims, YRT_STACK_DEPTH, d->gpu);
+  if (morton && d->gpu) HIP_CHECK(hipSetDevice(d->hipDevice));  // the build's kernels run in d->stream
+  gpu = build_gpu_scene(prims, YRT_STACK_DEPTH, d->gpu, morton, d->gpu ? d->stream : nullptr, d->kernelTiming);
 }
 
 }  // namespace yrt

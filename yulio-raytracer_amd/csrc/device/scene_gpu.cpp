@@ -70,7 +70,7 @@ GpuLight gpu_light_record(const LightInst& L) {
 }
 
 std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<ScenePrim>>& prims, int stackDepth,
-                                          bool upload) {
+                                          bool upload, bool morton, hipStream_t stream, bool timing) {
   auto t0 = std::chrono::steady_clock::now();
   auto S = std::make_shared<GpuScene>();
   if (upload) HIP_CHECK(hipGetDevice(&S->device));
@@ -276,7 +276,24 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
   if (gidBase >= (1 << 26)) throw std::runtime_error("scene exceeds 2^26 triangles (stack entry packing)");
 
   BvhResult bvh;
-  build_bvh(triVerts, triFlags, stackDepth, bvh, anyMotion ? &triVerts1 : nullptr);
+  {
+    const auto tb = std::chrono::steady_clock::now();
+    const std::vector<float>* v1 = anyMotion ? &triVerts1 : nullptr;
+    BuildInfo& bi = S->buildInfo;
+    S->mortonAsked = morton;
+    if (morton) {
+      bi.builder = upload ? BUILDER_MORTON_GPU : BUILDER_MORTON_HOST;
+      bi.fallback = upload ? build_bvh_morton_gpu(triVerts, triFlags, stackDepth, bvh, v1, stream, timing, &bi.msKernels)
+                           : build_bvh_morton_host(triVerts, triFlags, stackDepth, bvh, v1);
+    }
+    if (!morton || bi.fallback != FALLBACK_NONE) {
+      bi.builder = BUILDER_SAH;
+      bi.msKernels = 0;
+      build_bvh(triVerts, triFlags, stackDepth, bvh, v1);
+    }
+    bi.msBuild = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
+    bi.sahCost = bvh_sah_cost(bvh.nodes);
+  }
   // each leaf record carries its triangle's geometry id (GpuTri::e2[3]): part of the record's
   // layout as exported; the kernels take the id from the shading record (GpuTriShade)
   for (size_t i = 0; i < bvh.tris.size(); ++i) memcpy(&bvh.tris[i].e2[3], &triGeom[bvh.order[i]], 4);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../kernels/yrt_kernels.h"
+#include "bvh_build.h"
 #include "objects.h"
 #include "sampler.h"
 
@@ -84,6 +85,8 @@ struct GpuScene {
   int refits = 0;               // refit commits since the build (stats)
   int numTris = 0, numGeoms = 0, bvhDepth = 0;
   double buildSeconds = 0;
+  bool mortonAsked = false;     // the builder this tree was asked of (a commit that asks for the other one rebuilds)
+  BuildInfo buildInfo;          // the BVH step of the build (yrtGetSceneBuildInfo)
   float bboxLo[3] = {0, 0, 0}, bboxHi[3] = {0, 0, 0};
 };
 
@@ -91,8 +94,11 @@ struct GpuScene {
 // slot): what the light samplers read. build_gpu_scene fills those in.
 GpuLight gpu_light_record(const LightInst& L);
 
+// morton: the scene builder "morton" (bvh_build.h) instead of the host SAH builder: on the GPU in
+// `stream` when the scene is uploaded, else its host loop; timing: HIP-event time of its kernels
 std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<ScenePrim>>& prims, int stackDepth,
-                                          bool upload);
+                                          bool upload, bool morton = false, hipStream_t stream = nullptr,
+                                          bool timing = false);
 // A copy of an uploaded scene's device buffers on another HIP device (peer copies over xGMI),
 // for multi-GPU tile rendering; the host-side mirrors stay with the source.
 std::shared_ptr<GpuScene> replicate_gpu_scene(const GpuScene& src, int device);

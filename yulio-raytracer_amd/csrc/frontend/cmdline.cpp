@@ -271,7 +271,7 @@ void RtState::parseCommandLine(const std::vector<std::string>& tokens, const std
     } else if (tag == "-refine") cin.getInt();
     else if (tag == "-scene") sceneType = cin.get();
     else if (tag == "-accel") accel = cin.get();
-    else if (tag == "-builder") builder = cin.get();
+    else if (tag == "-builder") builder = cin.get();  // "morton": BVH built on the GPU (yrt_device.h); else host SAH
     else if (tag == "-traverser") traverser = cin.get();
     else if (tag == "-renderer") {
       const std::string r = cin.get();

@@ -417,6 +417,14 @@ class Device:
         d["bboxLo"], d["bboxHi"] = list(s.bboxLo), list(s.bboxHi)
         return d
 
+    def scene_build_info(self, scene) -> dict:
+        """The BVH step of the scene's last build (yrtGetSceneBuildInfo): builder (0 host SAH,
+        1 morton on the GPU, 2 morton's host loop), fallback, msBuild, msKernels, sahCost."""
+        s = N.SceneBuildInfo()
+        s.size = C.sizeof(s)
+        self._rc(N.dev.yrtGetSceneBuildInfo(self.h, scene, C.byref(s)), "scene_build_info")
+        return {n: getattr(s, n) for n, _ in s._fields_ if n not in ("size", "pad")}
+
     def export_bvh(self, scene):
         """Host mirror of the uploaded BVH: (nodes uint8[numNodes*128],
         tris uint8[numTriRefs*triRecordBytes])."""

@@ -57,6 +57,12 @@ class SceneInfo(C.Structure):
                 ("triRecordBytes", C.c_int64), ("nodeBytesClosest", C.c_int64), ("nodeBytesAny", C.c_int64)]
 
 
+class SceneBuildInfo(C.Structure):
+    """include/yrt_device.h YRTSceneBuildInfo; size = the bytes the caller's struct holds."""
+    _fields_ = [("size", C.c_uint32), ("builder", C.c_int32), ("fallback", C.c_int32), ("pad", C.c_int32),
+                ("msBuild", C.c_double), ("msKernels", C.c_double), ("sahCost", C.c_double)]
+
+
 class SessionInfo(C.Structure):
     _fields_ = [("device", vp), ("renderer", vp), ("tonemapper", vp), ("framebuffer", vp), ("scene", vp),
                 ("width", i32), ("height", i32), ("stereo", i32), ("numFrames", i32),
@@ -147,6 +153,10 @@ _sig(dev, "yrtGetRenderStats", i32, vp, C.POINTER(RenderStats))
 _sig(dev, "yrtSetKernelTiming", i32, vp, i32)
 _sig(dev, "yrtSetLanes", i32, vp, i32)
 _sig(dev, "yrtGetSceneInfo", i32, vp, vp, C.POINTER(SceneInfo))
+try:  # the scene builder's report; absent from older builds selected with YRT_LIB_DIR
+    _sig(dev, "yrtGetSceneBuildInfo", i32, vp, vp, C.POINTER(SceneBuildInfo))
+except AttributeError:
+    pass
 _sig(dev, "yrtExportBVH", i32, vp, vp, vp, sz, vp, sz)
 try:  # round 6; absent from older builds selected with YRT_LIB_DIR (same-box A/B against round 5)
     _sig(dev, "yrtExportQuantizedBVH", i32, vp, vp, vp, sz)
