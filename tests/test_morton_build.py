@@ -1,8 +1,8 @@
 """The scene builder "morton" (rtSetString(scene, "builder", "morton"): an LBVH over 63-bit Morton
-keys collapsed to the 4-wide nodes; common/yrt_lbvh.h, kernels/k_bvh_build.h, the host loop in
-device/bvh_build.cpp) against what the triangles and the topology determine (tests/refit_ref.py,
-test_refit._check_state) and against brute force. Hits do not depend on the tree, so nothing here
-has a tolerance: exports are compared byte for byte, hits bit for bit.
+keys collapsed to the 4-wide nodes; common/yrt_lbvh.h, yrt_bvh4.h, kernels/k_bvh_build.h, the host
+loop in device/bvh_build.cpp) against what the triangles and the topology determine
+(tests/refit_ref.py, test_refit._check_state) and against brute force. Hits do not depend on the
+tree, so nothing here has a tolerance: exports are compared byte for byte, hits bit for bit.
 
 The CPU tests run the builder's host loop (builder 2) on the host device; the GPU tests require the
 kernels (builder 1) to give the host loop's bytes, on every run.
@@ -271,6 +271,53 @@ def test_fallbacks(host_device):
     assert (k[:4096] == 0).all() and np.array_equal(k[4096:4159], np.uint64(1) << np.arange(63, dtype=np.uint64))
     assert _check_state(S) == 0
     assert S.info["bvhDepth"] <= 63
+
+
+def _inner(children, ni):
+    """The node indices of node ni's inner children, in slot order."""
+    c = children[ni][children[ni] != -1]
+    return [int(x) >> 5 for x in c if x & 31 == 0]
+
+
+@pytest.mark.parametrize("name", ["refit", "soup257"])
+def test_node_numbering_of_both_builders(host_device, name):
+    """Both builders write their nodes through one writer (common/yrt_bvh4.h) and number them
+    themselves. Default builder: depth-first pre-order, node 0 the root; the walk from the root that
+    visits a node's inner children in slot order meets the nodes as 0, 1, 2, ... "morton":
+    breadth-first; the inner children of a level's nodes, in node and then slot order, are the
+    consecutive indices after the level. Both: an empty slot is child -1 with lo = +inf, hi = -inf
+    on every axis; the pad is 0. No tolerance."""
+    S = SCENES[name](host_device)
+    trees = {}
+    for b in ("default", "morton"):
+        morton(S, b)
+        assert host_device.scene_build_info(S.scene)["builder"] == (2 if b == "morton" else 0)
+        planes, children, pad = rr.split_nodes(_exports(S)[0])
+        assert len(children) == S.info["numNodes"] > 4
+        empty = children == -1
+        assert empty.any() and not empty[0, :2].any()
+        lo, hi = planes[:, 0::2, :], planes[:, 1::2, :]          # (node, axis, child)
+        assert (lo.transpose(0, 2, 1)[empty] == np.inf).all() and (hi.transpose(0, 2, 1)[empty] == -np.inf).all()
+        assert np.isfinite(lo.transpose(0, 2, 1)[~empty]).all() and np.isfinite(hi.transpose(0, 2, 1)[~empty]).all()
+        assert not pad.any()
+        trees[b] = children
+    # depth-first pre-order
+    children = trees["default"]
+    order, stack = [], [0]
+    while stack:
+        ni = stack.pop()
+        order.append(ni)
+        stack += reversed(_inner(children, ni))
+    assert order == list(range(len(children)))
+    # breadth-first
+    children = trees["morton"]
+    level, after = [0], 1
+    while level:
+        nxt = [c for ni in level for c in _inner(children, ni)]
+        assert nxt == list(range(after, after + len(nxt))), (level[:4], nxt[:8], after)
+        level, after = nxt, after + len(nxt)
+    assert after == len(children)
+    assert any(len(_inner(children, ni)) > 1 for ni in range(len(children))), "no node with two inner children"
 
 
 # measured ratios morton / SAH (the module docstring has the figures), plus 10 %: the inputs are

@@ -3,7 +3,9 @@
 // Everything the kernels read is a flat array uploaded once per rtCommit(scene)
 // (the reference rebuilt the Embree BVH at every commit, api/scene_flat.h:72-97).
 //
-//  BVH (4-wide, collapsed from a binned-SAH BVH2 built on the host — device/bvh_build.cpp):
+//  BVH (4-wide, collapsed from a binary tree: a binned-SAH one built on the host, or the scene
+//  builder "morton"'s radix tree — device/bvh_build.cpp; yrt_bvh4.h is the one writer of both
+//  records):
 //    GpuNode  128 B  the four children's AABBs as planes [axis lo/hi][child] (so a packed
 //                    op tests two children's planes at once) + four child references
 //                    (index << 5 | count: count 0 = inner node, 1..31 = leaf triangle

@@ -1,24 +1,24 @@
-// yrt_lbvh.h — the per-element steps of the "morton" scene builder (LBVH, Karras 2012, collapsed
-// to 4-wide nodes), written once: the kernels of kernels/k_bvh_build.h and the serial host loop of
-// device/bvh_build.cpp call the same functions, so both give the same bytes (-ffp-contract=off on
-// both sides, comparisons instead of fmin / fmax so that +0 / -0 and the operand order are spelled
-// out), as yrt_qnode.h and yrt_tri_record.h do for the quantizer and the leaf records.
+// yrt_lbvh.h — the Morton-specific per-element steps of the scene builder "morton" (LBVH, Karras
+// 2012, collapsed to 4-wide nodes), written once: the kernels of kernels/k_bvh_build.h and the
+// serial host loop of device/bvh_build.cpp call the same functions, so both give the same bytes.
+// What the builder shares with the host SAH builders (the box, the binary node, the collapse rule,
+// the node and leaf-record writers) is yrt_bvh4.h's.
 //
-//   1 lbvh_prim_box     vertex bounds of a triangle (both ends of the frame time), finiteness
-//   2 lbvh_key          63-bit Morton code of the box centre inside the centroid bounds
-//   3 lbvh_range        node i of the N - 1 radix-tree nodes: its key range and split
-//     lbvh_node2        the node's two child references; a range of <= YRT_MAX_LEAF keys is a leaf
-//   5 lbvh_child_box    a child's box, bottom-up: the exact union of its triangles' / its node's boxes
-//   6 lbvh_collapse     Collapser::collapse's rule for one 4-wide node (device/bvh_build.cpp)
-//     lbvh_emit         the 128-B node
-//   9 lbvh_leaf_record  the leaf record of a sorted slot
+//   1 lbvh_prim_box       vertex bounds of a triangle (both ends of the frame time), finiteness
+//   2 lbvh_key            63-bit Morton code of the box centre inside the centroid bounds
+//   3 lbvh_range          node i of the N - 1 radix-tree nodes: its key range and split
+//     lbvh_node2          the node's two child references; a range of <= YRT_MAX_LEAF keys is a leaf
+//   5 lbvh_child_box      a child's box, bottom-up: the exact union of its triangles' / its node's boxes
+//   6 collapse4           the children of one 4-wide node (yrt_bvh4.h)
+//   7 lbvh_number         breadth-first numbering: a level's inner children follow the level
+//     write_node4         the 128-B node (yrt_bvh4.h)
+//   9 write_leaf_record   the leaf record of a sorted slot (yrt_bvh4.h)
 #pragma once
 
 #include <math.h>
 #include <stdint.h>
 
-#include "yrt_gpu_types.h"
-#include "yrt_tri_record.h"
+#include "yrt_bvh4.h"
 
 #ifndef YRT_MAX_LEAF
 #define YRT_MAX_LEAF 8
@@ -28,62 +28,24 @@
 
 namespace yrt {
 
-struct LbvhBox {
-  float lo[3], hi[3];
-};
-
-// A radix-tree node as the collapse reads it (bvh_build.cpp Node2): cnt 0: inner node idx;
-// cnt > 0: the leaf of sorted slots [idx, idx + cnt)
-struct LbvhNode2 {
-  LbvhBox b[2];
-  int idx[2], cnt[2];
-};
-
-struct LbvhRef {
-  LbvhBox b;
-  int idx, cnt;
-};
-
-YRT_THD void lbvh_box_reset(LbvhBox& b) {
-  for (int k = 0; k < 3; ++k) { b.lo[k] = INFINITY; b.hi[k] = -INFINITY; }
-}
-YRT_THD void lbvh_box_grow(LbvhBox& a, const LbvhBox& b) {
-  for (int k = 0; k < 3; ++k) {
-    a.lo[k] = b.lo[k] < a.lo[k] ? b.lo[k] : a.lo[k];
-    a.hi[k] = b.hi[k] > a.hi[k] ? b.hi[k] : a.hi[k];
-  }
-}
-// Box::area of bvh_build.cpp
-YRT_THD float lbvh_box_area(const LbvhBox& b) {
-  const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
-  if (!(dx >= 0 && dy >= 0 && dz >= 0)) return 0.f;
-  return 2.f * (dx * dy + dy * dz + dz * dx);
-}
-
 // ---------------------------------------------------------------- 1 primitive box
 // v, v1: the triangle's 9 floats at time 0 and (moving scenes, else null) time 1. Returns false
 // when a coordinate or the box centre is not finite.
-YRT_THD bool lbvh_prim_box(const float* v, const float* v1, LbvhBox& b) {
-  lbvh_box_reset(b);
+YRT_THD bool lbvh_prim_box(const float* v, const float* v1, Box& b) {
+  b.reset();
   bool ok = true;
   for (int s = 0; s < 2; ++s) {
     const float* p = s ? v1 : v;
     if (!p) continue;
-    for (int j = 0; j < 9; ++j) {
-      const float x = p[j];
-      const int k = j % 3;
-      ok = ok && (x - x == 0.f);
-      b.lo[k] = x < b.lo[k] ? x : b.lo[k];
-      b.hi[k] = x > b.hi[k] ? x : b.hi[k];
-    }
+    for (int j = 0; j < 9; ++j) ok = ok && (p[j] - p[j] == 0.f);
+    for (int j = 0; j < 3; ++j) b.growP(p + 3 * j);
   }
   for (int k = 0; k < 3; ++k) {
-    const float c = 0.5f * (b.lo[k] + b.hi[k]);
+    const float c = b.centre(k);
     ok = ok && (c - c == 0.f);
   }
   return ok;
 }
-YRT_THD float lbvh_centroid(const LbvhBox& b, int k) { return 0.5f * (b.lo[k] + b.hi[k]); }
 
 // ---------------------------------------------------------------- 2 key
 // q = min(2^21 - 1, (int)((c - lo) * (2^21 / (hi - lo)))); 0 on an axis without extent (and where
@@ -106,10 +68,10 @@ YRT_THD uint64_t lbvh_spread(uint32_t q) {
   return x;
 }
 // x, y, z interleaved from bit 62 down; cb: the bounds of all box centres
-YRT_THD uint64_t lbvh_key(const LbvhBox& b, const LbvhBox& cb) {
+YRT_THD uint64_t lbvh_key(const Box& b, const Box& cb) {
   uint64_t key = 0;
   for (int k = 0; k < 3; ++k)
-    key |= lbvh_spread(lbvh_quantize(lbvh_centroid(b, k), cb.lo[k], cb.hi[k])) << (2 - k);
+    key |= lbvh_spread(lbvh_quantize(b.centre(k), cb.lo[k], cb.hi[k])) << (2 - k);
   return key;
 }
 
@@ -147,7 +109,7 @@ YRT_THD void lbvh_range(const uint64_t* keys, int n, int i, int& first, int& las
 YRT_THD bool lbvh_is_inner(int i, int first, int last) { return i == 0 || last - first + 1 > YRT_MAX_LEAF; }
 // The child references of node i (boxes left alone): the left child is node `split` or a leaf,
 // the right child node `split + 1` or a leaf.
-YRT_THD void lbvh_node2(int first, int last, int split, LbvhNode2& n) {
+YRT_THD void lbvh_node2(int first, int last, int split, Node2& n) {
   const int lo[2] = {first, split + 1}, hi[2] = {split, last};
   for (int c = 0; c < 2; ++c) {
     const int cnt = hi[c] - lo[c] + 1;
@@ -160,81 +122,31 @@ YRT_THD void lbvh_node2(int first, int last, int split, LbvhNode2& n) {
 // ---------------------------------------------------------------- 5 boxes
 // Box of child c of a node whose inner children are done (deeper level): the union of the leaf's
 // triangles in slot order, or of the inner node's two child boxes.
-YRT_THD void lbvh_child_box(const LbvhNode2* nodes, const LbvhBox* primBox, const uint32_t* slotId, int i, int c,
-                            LbvhBox& b) {
-  lbvh_box_reset(b);
+YRT_THD void lbvh_child_box(const Node2* nodes, const Box* primBox, const uint32_t* slotId, int i, int c,
+                            Box& b) {
+  b.reset();
   const int idx = nodes[i].idx[c], cnt = nodes[i].cnt[c];
   if (cnt > 0) {
-    for (int t = 0; t < cnt; ++t) lbvh_box_grow(b, primBox[slotId[idx + t]]);
+    for (int t = 0; t < cnt; ++t) b.grow(primBox[slotId[idx + t]]);
   } else {
-    lbvh_box_grow(b, nodes[idx].b[0]);
-    lbvh_box_grow(b, nodes[idx].b[1]);
+    b.grow(nodes[idx].b[0]);
+    b.grow(nodes[idx].b[1]);
   }
 }
 
-// ---------------------------------------------------------------- 6 collapse
-// The children of the 4-wide node made from radix-tree node n2: its two children; then, until
-// there are four, the inner child of the largest area (ties: the lowest slot) is opened, its left
-// child takes the slot and its right child the next free one. Returns the child count (2 .. 4).
-YRT_THD int lbvh_collapse(const LbvhNode2* in, int n2, LbvhRef ch[4]) {
-  int k = 2;
-  for (int j = 0; j < 2; ++j) { ch[j].b = in[n2].b[j]; ch[j].idx = in[n2].idx[j]; ch[j].cnt = in[n2].cnt[j]; }
-  while (k < 4) {
-    int best = -1;
-    float bestArea = -1.f;
-    for (int j = 0; j < k; ++j) {
-      if (ch[j].cnt != 0) continue;
-      const float a = lbvh_box_area(ch[j].b);
-      if (a > bestArea) { bestArea = a; best = j; }
-    }
-    if (best < 0) break;
-    const int o = ch[best].idx;
-    ch[best].b = in[o].b[0]; ch[best].idx = in[o].idx[0]; ch[best].cnt = in[o].cnt[0];
-    ch[k].b = in[o].b[1]; ch[k].idx = in[o].idx[1]; ch[k].cnt = in[o].cnt[1];
-    ++k;
-  }
-  return k;
-}
-YRT_THD int lbvh_count_inner(const LbvhRef ch[4], int k) {
+// ---------------------------------------------------------------- 7 numbering
+YRT_THD int lbvh_count_inner(const Ref ch[4], int k) {
   int n = 0;
   for (int j = 0; j < k; ++j) n += ch[j].cnt == 0;
   return n;
 }
-// The 128-B node of children ch[0 .. k): leaves as (slot << 5) | count, the r-th inner child (slot
-// order) as node firstInner + r; empty slots the inverted infinite box and -1 (bvh_build.cpp).
-// next (k entries at most): the inner children's radix-tree nodes in the same order.
-YRT_THD void lbvh_emit(GpuNode& g, const LbvhRef ch[4], int k, int firstInner, int* next) {
+// Breadth-first: the r-th inner child (slot order) of ch[0 .. k) is node firstInner + r, and
+// next[r] its radix-tree node. Returns the number of inner children.
+YRT_THD int lbvh_number(const Ref ch[4], int k, int firstInner, int node[4], int next[4]) {
   int r = 0;
-  for (int j = 0; j < 4; ++j) {
-    const bool v = j < k;
-    const float L = INFINITY, H = -INFINITY;
-    g.lox[j] = v ? ch[j].b.lo[0] : L; g.hix[j] = v ? ch[j].b.hi[0] : H;
-    g.loy[j] = v ? ch[j].b.lo[1] : L; g.hiy[j] = v ? ch[j].b.hi[1] : H;
-    g.loz[j] = v ? ch[j].b.lo[2] : L; g.hiz[j] = v ? ch[j].b.hi[2] : H;
-    g.pad[j] = 0;
-    if (!v) {
-      g.child[j] = -1;
-    } else if (ch[j].cnt > 0) {
-      g.child[j] = (ch[j].idx << 5) | ch[j].cnt;
-    } else {
-      next[r] = ch[j].idx;
-      g.child[j] = (firstInner + r) << 5;
-      ++r;
-    }
-  }
-}
-
-// ---------------------------------------------------------------- 9 leaf records
-// v: 9 floats per triangle id; the .w words as build_bvh writes them (id, flags, 0)
-YRT_THD void lbvh_leaf_record(GpuTri& g, const float* v, const uint32_t* flags, uint32_t id) {
-  const float* t = v + (size_t)id * 9;
-  yrt_tri_vertices(g, t, t + 3, t + 6);
-  union { uint32_t u; float f; } a, b;
-  a.u = id;
-  b.u = flags[id];
-  g.v0[3] = a.f;
-  g.e1[3] = b.f;
-  g.e2[3] = 0.f;
+  for (int j = 0; j < k; ++j)
+    if (ch[j].cnt == 0) { node[j] = firstInner + r; next[r++] = ch[j].idx; }
+  return r;
 }
 
 }  // namespace yrt

@@ -1,6 +1,7 @@
-// bvh_build.h — host 4-wide BVH builder (see bvh_build.cpp).
+// bvh_build.h — the 4-wide BVH builders (see bvh_build.cpp, kernels/bvh_build.hip).
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
@@ -24,16 +25,38 @@ void build_bvh(const std::vector<float>& v, const std::vector<uint32_t>& flags, 
 
 // ---------------------------------------------------------------- scene builder "morton"
 // An LBVH (63-bit Morton keys, Karras 2012) collapsed to the same 4-wide nodes; the steps are in
-// common/yrt_lbvh.h. The result depends on the triangles alone: the serial host loop and the
-// kernels (kernels/bvh_build.hip) give the same bytes on every run. Both take build_bvh's
-// arguments and return 0 with `out` filled, or the reason why the caller has to use build_bvh:
+// common/yrt_lbvh.h and common/yrt_bvh4.h. The result depends on the triangles alone: the serial
+// host loop and the kernels (kernels/bvh_build.hip) give the same bytes on every run. Both take
+// build_bvh's arguments and return 0 with `out` filled, or the reason why the caller has to use build_bvh:
 enum BuildFallback {
   FALLBACK_NONE = 0,
   FALLBACK_FEW_TRIANGLES = 1,  // fewer than 2
   FALLBACK_NON_FINITE = 2,     // a vertex (or a box centre) is not finite
   FALLBACK_STACK = 3,          // the worst-case traversal stack exceeds stackDepth - 1
-  FALLBACK_SIZE = 4            // node / reference limits of build_bvh
+  FALLBACK_SIZE = 4            // node / reference limits (bvh_limits)
 };
+// What every tree has to meet, whoever built it: the worst-case traversal stack fits the kernels'
+// (stackDepth - 1 entries), and a child reference packs (index << 5) | count into an int while
+// the traversal addresses a node by a 32-bit byte offset, (index << 6) for the quantized nodes
+// (kernels/yrt_traverse.h qnode_load) and (index << 7) for the float ones: 2^25 nodes, 2^26 leaf
+// triangle references. Returns FALLBACK_NONE or the limit that is exceeded (why: in words).
+inline BuildFallback bvh_limits(size_t numNodes, size_t numRefs, int maxStack, int stackDepth,
+                                const char** why = nullptr) {
+  const char* w = nullptr;
+  BuildFallback f = FALLBACK_NONE;
+  if (maxStack > stackDepth - 1) {
+    f = FALLBACK_STACK;
+    w = "BVH traversal stack bound exceeds YRT_STACK_DEPTH";
+  } else if (numNodes >= (size_t(1) << 25)) {
+    f = FALLBACK_SIZE;
+    w = "BVH exceeds 2^25 nodes (32-bit node byte offsets)";
+  } else if (numRefs >= (size_t(1) << 26)) {
+    f = FALLBACK_SIZE;
+    w = "BVH exceeds 2^26 leaf triangle references (child reference packing)";
+  }
+  if (why) *why = w;
+  return f;
+}
 enum BuilderKind { BUILDER_SAH = 0, BUILDER_MORTON_GPU = 1, BUILDER_MORTON_HOST = 2 };
 int build_bvh_morton_host(const std::vector<float>& v, const std::vector<uint32_t>& flags, int stackDepth,
                           BvhResult& out, const std::vector<float>* v1 = nullptr);

@@ -85,7 +85,8 @@ int build_bvh_morton_gpu(const std::vector<float>& v, const std::vector<uint32_t
   if (msKernels) *msKernels = 0;
   const size_t N64 = v.size() / 9;
   if (N64 < 2) return FALLBACK_FEW_TRIANGLES;
-  if (N64 >= (size_t(1) << 26) || flags.size() < N64 || (v1 && v1->size() < N64 * 9)) return FALLBACK_SIZE;
+  if (BuildFallback f = bvh_limits(0, N64, 0, stackDepth)) return f;
+  if (flags.size() < N64 || (v1 && v1->size() < N64 * 9)) return FALLBACK_SIZE;
   const int N = (int)N64, M = N - 1;  // M radix-tree nodes
 
   // temporaries, all sized from N before the first launch
@@ -102,13 +103,13 @@ int build_bvh_morton_gpu(const std::vector<float>& v, const std::vector<uint32_t
   dV.alloc(N64 * 9 * sizeof(float));
   if (v1) dV1.alloc(N64 * 9 * sizeof(float));
   dFlags.alloc(N64 * sizeof(uint32_t));
-  dBox.alloc(N64 * sizeof(LbvhBox));
+  dBox.alloc(N64 * sizeof(Box));
   dState.alloc(sizeof(LbvhState));
   dKeyA.alloc(N64 * 8);
   dKeyB.alloc(N64 * 8);
   dIdA.alloc(N64 * 4);
   dSlot.alloc(N64 * 4);
-  dNodes2.alloc((size_t)M * sizeof(LbvhNode2));
+  dNodes2.alloc((size_t)M * sizeof(Node2));
   dParent.alloc((size_t)M * 4);
   dInner.alloc((size_t)M * 4);
   dDepthA.alloc((size_t)M * 4);
@@ -131,13 +132,13 @@ int build_bvh_morton_gpu(const std::vector<float>& v, const std::vector<uint32_t
   Segments seg(s, timing);
   LbvhState* st = dState.as<LbvhState>();
   k_lbvh_prims<<<blocks(N), YRT_LBVH_BLOCK, 0, s>>>(dV.as<float>(), v1 ? dV1.as<float>() : nullptr, N,
-                                                    dBox.as<LbvhBox>(), st);
-  k_lbvh_keys<<<blocks(N), YRT_LBVH_BLOCK, 0, s>>>(dBox.as<LbvhBox>(), st, N, dKeyA.as<uint64_t>(),
+                                                    dBox.as<Box>(), st);
+  k_lbvh_keys<<<blocks(N), YRT_LBVH_BLOCK, 0, s>>>(dBox.as<Box>(), st, N, dKeyA.as<uint64_t>(),
                                                    dIdA.as<uint32_t>());
   size_t tb = tmpBytes;
   LBVH_CHECK(rocprim::radix_sort_pairs(dTemp.p, tb, dKeyA.as<uint64_t>(), dKeyB.as<uint64_t>(), dIdA.as<uint32_t>(),
                                        dSlot.as<uint32_t>(), (size_t)N, 0u, 63u, s));
-  k_lbvh_hierarchy<<<blocks(M), YRT_LBVH_BLOCK, 0, s>>>(dKeyB.as<uint64_t>(), N, dNodes2.as<LbvhNode2>(),
+  k_lbvh_hierarchy<<<blocks(M), YRT_LBVH_BLOCK, 0, s>>>(dKeyB.as<uint64_t>(), N, dNodes2.as<Node2>(),
                                                         dParent.as<int>(), dInner.as<int>());
   k_lbvh_depth<<<blocks(M), YRT_LBVH_BLOCK, 0, s>>>(dParent.as<int>(), dInner.as<int>(), M, dDepthA.as<uint32_t>(),
                                                     dNodeA.as<uint32_t>(), st);
@@ -157,7 +158,7 @@ int build_bvh_morton_gpu(const std::vector<float>& v, const std::vector<uint32_t
 
   for (int d = h.numLevels - 1; d >= 0; --d) {
     const int cnt = h.levelStart[d + 1] - h.levelStart[d];
-    k_lbvh_boxes<<<blocks(cnt), YRT_LBVH_BLOCK, 0, s>>>(dNodes2.as<LbvhNode2>(), dBox.as<LbvhBox>(),
+    k_lbvh_boxes<<<blocks(cnt), YRT_LBVH_BLOCK, 0, s>>>(dNodes2.as<Node2>(), dBox.as<Box>(),
                                                         dSlot.as<uint32_t>(),
                                                         dLevelNodes.as<uint32_t>() + h.levelStart[d], cnt);
   }
@@ -171,13 +172,13 @@ int build_bvh_morton_gpu(const std::vector<float>& v, const std::vector<uint32_t
   int *front = dFrontA.as<int>(), *next = dFrontB.as<int>(), *stk = dStackA.as<int>(), *nstk = dStackB.as<int>();
   for (int level = 0; cnt > 0; ++level) {
     if (level >= YRT_LBVH_MAX_LEVELS) return FALLBACK_STACK;
-    if ((size_t)base + (size_t)cnt >= (size_t(1) << 25)) return FALLBACK_SIZE;
+    if (BuildFallback f = bvh_limits((size_t)base + (size_t)cnt, N64, 0, stackDepth)) return f;
     if (base + cnt > live) throw std::runtime_error("morton build: more 4-wide nodes than radix-tree nodes");
-    k_lbvh_count<<<blocks(cnt), YRT_LBVH_BLOCK, 0, s>>>(dNodes2.as<LbvhNode2>(), front, cnt, dNumInner.as<int>());
+    k_lbvh_count<<<blocks(cnt), YRT_LBVH_BLOCK, 0, s>>>(dNodes2.as<Node2>(), front, cnt, dNumInner.as<int>());
     tb = tmpBytes;
     LBVH_CHECK(rocprim::exclusive_scan(dTemp.p, tb, dNumInner.as<int>(), dOff.as<int>(), 0, (size_t)cnt,
                                        rocprim::plus<int>(), s));
-    k_lbvh_emit<<<blocks(cnt), YRT_LBVH_BLOCK, 0, s>>>(dNodes2.as<LbvhNode2>(), front, stk, dOff.as<int>(), cnt, base,
+    k_lbvh_emit<<<blocks(cnt), YRT_LBVH_BLOCK, 0, s>>>(dNodes2.as<Node2>(), front, stk, dOff.as<int>(), cnt, base,
                                                        dOut.as<GpuNode>(), next, nstk, live, st);
     LBVH_CHECK(hipGetLastError());
     LBVH_CHECK(hipMemcpyAsync(&h.maxStack, &st->maxStack, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -189,7 +190,7 @@ int build_bvh_morton_gpu(const std::vector<float>& v, const std::vector<uint32_t
     std::swap(front, next);
     std::swap(stk, nstk);
   }
-  if (h.maxStack > stackDepth - 1) return FALLBACK_STACK;
+  if (BuildFallback f = bvh_limits((size_t)base, N64, h.maxStack, stackDepth)) return f;
 
   k_lbvh_leaves<<<blocks(N), YRT_LBVH_BLOCK, 0, s>>>(dV.as<float>(), dFlags.as<uint32_t>(), dSlot.as<uint32_t>(), N,
                                                      dTris.as<GpuTri>());

@@ -1,9 +1,10 @@
 // k_bvh_build.h — the kernels of the scene builder "morton": one thread per element, 64-thread
-// blocks, every step one of common/yrt_lbvh.h's functions (the host loop of device/bvh_build.cpp
-// calls the same ones). No kernel reads what another workgroup of the same launch wrote: a kernel
-// boundary is the only hand-over (the XCDs' L2s are private), nothing polls or waits, and the only
-// atomics are reductions (centroid bounds, flags, the stack bound) that the next launch or the
-// host reads. Every index used as an address derives from N, which the host checked.
+// blocks, every step one of common/yrt_lbvh.h's and yrt_bvh4.h's functions (the host loop of
+// device/bvh_build.cpp calls the same ones). No kernel reads what another workgroup of the same
+// launch wrote: a kernel boundary is the only hand-over (the XCDs' L2s are private), nothing polls
+// or waits, and the only atomics are reductions (centroid bounds, flags, the stack bound) that the
+// next launch or the host reads. Every index used as an address derives from N, which the host
+// checked.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,42 +37,41 @@ struct LbvhState {
 
 // 1 boxes and centroid bounds
 __global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_prims(const float* __restrict__ v, const float* __restrict__ v1,
-                                                              int N, LbvhBox* __restrict__ primBox,
+                                                              int N, Box* __restrict__ primBox,
                                                               LbvhState* __restrict__ st) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  Box cb;  // this lane's part of the centroid bounds: empty, or its box centre
+  cb.reset();
   bool bad = false;
   if (i < N) {
-    LbvhBox b;
+    Box b;
     bad = !lbvh_prim_box(v + (size_t)i * 9, v1 ? v1 + (size_t)i * 9 : nullptr, b);
     primBox[i] = b;
-    for (int k = 0; k < 3; ++k) lo[k] = hi[k] = lbvh_centroid(b, k);
+    for (int k = 0; k < 3; ++k) cb.lo[k] = cb.hi[k] = b.centre(k);
   }
-  for (int k = 0; k < 3; ++k) {
-    for (int m = 32; m >= 1; m >>= 1) {
-      const float a = __shfl_xor(lo[k], m), c = __shfl_xor(hi[k], m);
-      lo[k] = a < lo[k] ? a : lo[k];
-      hi[k] = c > hi[k] ? c : hi[k];
-    }
+  for (int m = 32; m >= 1; m >>= 1) {
+    Box o;
+    for (int k = 0; k < 3; ++k) { o.lo[k] = __shfl_xor(cb.lo[k], m); o.hi[k] = __shfl_xor(cb.hi[k], m); }
+    cb.grow(o);
   }
   const bool anyBad = __any(bad);
   if ((threadIdx.x & 63) == 0) {
     for (int k = 0; k < 3; ++k) {
       // a NaN centre is flagged, and never compared on: the bounds of a flagged scene are not used
-      atomicMin(&st->cbLo[k], lbvh_ordered(lo[k]));
-      atomicMax(&st->cbHi[k], lbvh_ordered(hi[k]));
+      atomicMin(&st->cbLo[k], lbvh_ordered(cb.lo[k]));
+      atomicMax(&st->cbHi[k], lbvh_ordered(cb.hi[k]));
     }
     if (anyBad) atomicOr(&st->nonFinite, 1);
   }
 }
 
 // 2 keys
-__global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_keys(const LbvhBox* __restrict__ primBox,
+__global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_keys(const Box* __restrict__ primBox,
                                                              const LbvhState* __restrict__ st, int N,
                                                              uint64_t* __restrict__ keys, uint32_t* __restrict__ ids) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
-  LbvhBox cb;
+  Box cb;
   for (int k = 0; k < 3; ++k) { cb.lo[k] = lbvh_unordered(st->cbLo[k]); cb.hi[k] = lbvh_unordered(st->cbHi[k]); }
   keys[i] = lbvh_key(primBox[i], cb);
   ids[i] = (uint32_t)i;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_keys(const LbvhBox* __r
 
 // 3, 4 hierarchy and leaves: node i of N - 1; parent[] starts at -1 and is written for inner children
 __global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_hierarchy(const uint64_t* __restrict__ keys, int N,
-                                                                  LbvhNode2* __restrict__ nodes,
+                                                                  Node2* __restrict__ nodes,
                                                                   int* __restrict__ parent, int* __restrict__ inner) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N - 1) return;
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_hierarchy(const uint64_
   const bool in = lbvh_is_inner(i, first, last);
   inner[i] = in ? 1 : 0;
   if (!in) return;
-  LbvhNode2 n;
+  Node2 n;
   lbvh_node2(first, last, split, n);
   for (int c = 0; c < 2; ++c) {
     nodes[i].idx[c] = n.idx[c];
@@ -137,33 +137,33 @@ __global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_level_starts(const uint
 }
 
 // 5 boxes of one level (deepest first)
-__global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_boxes(LbvhNode2* __restrict__ nodes,
-                                                              const LbvhBox* __restrict__ primBox,
+__global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_boxes(Node2* __restrict__ nodes,
+                                                              const Box* __restrict__ primBox,
                                                               const uint32_t* __restrict__ slotId,
                                                               const uint32_t* __restrict__ levelNodes, int count) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= count) return;
   const int i = (int)levelNodes[t];
   for (int c = 0; c < 2; ++c) {
-    LbvhBox b;
+    Box b;
     lbvh_child_box(nodes, primBox, slotId, i, c, b);
     nodes[i].b[c] = b;
   }
 }
 
 // 6, 7 collapse of one 4-wide level: count the inner children, (scan,) emit
-__global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_count(const LbvhNode2* __restrict__ nodes,
+__global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_count(const Node2* __restrict__ nodes,
                                                               const int* __restrict__ frontier, int count,
                                                               int* __restrict__ numInner) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= count) return;
-  LbvhRef ch[4];
-  const int k = lbvh_collapse(nodes, frontier[f], ch);
+  Ref ch[4];
+  const int k = collapse4(nodes, frontier[f], ch);
   numInner[f] = lbvh_count_inner(ch, k);
 }
 
 // node base + f; its inner children are nodes base + count + off[f] ..; cap: entries of next / nextStack
-__global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_emit(const LbvhNode2* __restrict__ nodes,
+__global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_emit(const Node2* __restrict__ nodes,
                                                              const int* __restrict__ frontier,
                                                              const int* __restrict__ stackAbove,
                                                              const int* __restrict__ off, int count, int base,
@@ -172,15 +172,15 @@ __global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_emit(const LbvhNode2* _
                                                              LbvhState* __restrict__ st) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= count) return;
-  LbvhRef ch[4];
-  const int k = lbvh_collapse(nodes, frontier[f], ch);
+  Ref ch[4];
+  const int k = collapse4(nodes, frontier[f], ch);
   const int stackHere = stackAbove[f] + (k - 1);
   atomicMax(&st->maxStack, stackHere);
-  int nx[4];
+  int node[4], nx[4];
+  const int ni = lbvh_number(ch, k, base + count + off[f], node, nx);
   GpuNode g;
-  lbvh_emit(g, ch, k, base + count + off[f], nx);
+  write_node4(g, ch, k, node);
   out[base + f] = g;
-  const int ni = lbvh_count_inner(ch, k);
   for (int r = 0; r < ni; ++r)
     if (off[f] + r < cap) { next[off[f] + r] = nx[r]; nextStack[off[f] + r] = stackHere; }
   if (f == count - 1) st->nextCount = off[f] + ni;
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(YRT_LBVH_BLOCK) void k_lbvh_leaves(const float* __r
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   GpuTri g;
-  lbvh_leaf_record(g, v, flags, slotId[i]);
+  write_leaf_record(g, v, flags, slotId[i]);
   tris[i] = g;
 }
 
