@@ -375,6 +375,25 @@ YRT_API int yrtDebugCheckMathTable(YRTDevice dev, int fn, const uint16_t* table2
  * with c; every index in the rows is checked before the launch. Not part of the renderer. */
 YRT_API int yrtDebugShade(YRTDevice dev, int mode, YRTHandle object, const float* rows, int n, const void* materials,
                           int numMaterials, float* out);
+/* Test-only probe of Material::shade and the texture lookup on the device (k_check_material,
+ * k_check_textures, kernels/k_checks.h), on one primitive of a committed, uploaded scene: the
+ * primitive's geometry record is read from the scene's uploaded records exactly as k_shade reads
+ * it. set: which of the shade kernel's material sets to instantiate ("uber", "obj", "spheres",
+ * "stereo", "collada", "all"); a material outside the named set is an error, not a launch.
+ * mode 0: rows n x 22 words (wo, Ns, Ng, Tx, Ty, wi, s.xy, dg.s, dg.t), medium4 the current medium
+ * (transmission rgb, eta; resolved to the scene's medium index by value), out n x 34 words: the
+ * component count, then 3 x (type flags, eval3, sample3, wi3, pdf), zero beyond the count.
+ * mode 1: rows n x 2 words (s, t), raw: the material's s0 / ds are not applied; out n x 24 words:
+ * RGBA of the lookup through each of the material's texture slots 0..4 (zero where unset), then
+ * RGBA of slot 0 through the descriptor copy in the geometry record. Not part of the renderer. */
+YRT_API int yrtDebugMaterial(YRTDevice dev, YRTHandle scene, YRTHandle primitive, int mode, const char* set,
+                             const float* medium4, const float* rows, int n, float* out);
+/* Test-only: the texture tables of a committed scene as the kernels read them. what 0: the image
+ * records (24 B: width, height, format, pad, int64 pool offset); 1: the texture records (32 B);
+ * 2: the row-major texel pool (8-bit images first); 3: the 2x2 footprint records of the pool's
+ * 8-bit part (16 B per texel at 4x the texel's byte offset). Returns the byte count, and copies
+ * when buf holds that many; -1 on error. Works on a host-only device too. */
+YRT_API int64_t yrtDebugTexturePool(YRTDevice dev, YRTHandle scene, int what, void* buf, size_t bytes);
 /* Test-only: the direction-term table of a sample table (kernels/k_sample_dirs.h). The frame
  * cache entry of the request (spp, sets, iteration, num1D, num2D, filter; no lights) is created
  * on the device's first GPU as a render would create it; dims receives its sample table

@@ -69,6 +69,8 @@ _sig("oracle_camera_rays_lens", i32, vp, sz, i32, vp, vp, vp, vp)
 _sig("oracle_brdf_comps", i32, i32, vp, i32, vp)
 _sig("oracle_brdf", i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp)
 _sig("oracle_material_components", i32, vp, sz, vp, i32, vp, vp)
+_sig("oracle_material_components_st", i32, vp, sz, vp, i32, vp, i32, vp)
+_sig("oracle_texture_get", i32, vp, sz, i32, i32, vp, vp)
 _sig("oracle_light_sample", i32, vp, sz, vp, i32, vp, vp, vp, vp, vp, vp)
 _sig("oracle_brdf_set_sample", i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp)
 
@@ -304,12 +306,26 @@ def brdf_set_sample(kinds, args, wo, frame, s, ss):
 
 def material_components(blob: bytes, medium4, rows):
     """Material::shade of the blob's material in the medium (T.rgb, eta) on rows (n, 20) = wo, Ns, Ng,
-    Tx, Ty, wi, s: (n, 34) = count, then 3 x (type bits, eval3, sample3, wi3, pdf)."""
-    rows, medium4 = _f32(rows, -1, 20), _f32(medium4, 4)
+    Tx, Ty, wi, s, or (n, 22) with the hit's texture coordinates dg.s, dg.t appended (the blob may
+    then hold images, textures and a textured material): (n, 34) = count, then 3 x (type bits,
+    eval3, sample3, wi3, pdf)."""
+    rows = np.ascontiguousarray(rows, np.float32)
+    words = 22 if rows.ndim == 2 and rows.shape[1] == 22 else 20
+    rows, medium4 = rows.reshape(-1, words), _f32(medium4, 4)
     out = np.zeros((rows.shape[0], 34), np.float32)
-    if _lib.oracle_material_components(blob, len(blob), medium4.ctypes.data, rows.shape[0], rows.ctypes.data,
-                                       out.ctypes.data):
+    if _lib.oracle_material_components_st(blob, len(blob), medium4.ctypes.data, rows.shape[0], rows.ctypes.data,
+                                          words, out.ctypes.data):
         raise RuntimeError(f"oracle_material_components: {_err()}")
+    return out
+
+
+def texture_get(blob: bytes, texture, s, t):
+    """Texture::get of the blob's texture object number `texture` (among its texture objects, in
+    blob order) at the raw coordinates (s[i], t[i]): RGBA float32 (n, 4)."""
+    st = np.ascontiguousarray(np.stack([np.asarray(s, np.float32).ravel(), np.asarray(t, np.float32).ravel()], 1))
+    out = np.zeros((st.shape[0], 4), np.float32)
+    if _lib.oracle_texture_get(blob, len(blob), int(texture), st.shape[0], st.ctypes.data, out.ctypes.data):
+        raise RuntimeError(f"oracle_texture_get: {_err()}")
     return out
 
 

@@ -33,10 +33,17 @@
 // restated call pattern).
 //
 // Material::shade of the nine texture-free materials is read back through the CompositedBRDF it
-// fills (ref_material_components below says how).
+// fills (ref_material_components below says how). Its recorded answers
+// (tests/golden/ref_shade_mat_*.npz) are compared with the oracle (tests/test_ref_shade.py) and
+// with the device's own shade_material, run by the probe k_check_material on a committed scene
+// (tests/test_ref_textures.py).
 //
-// Not built here (DESIGN.md §4 lists them as unpinned): the textured materials, textures,
-// postIntersect and the integrator.
+// Not built here: the textured materials, textures, postIntersect and the integrator. Textures
+// and the textured materials have no live reference witness (Bilinear.h, nearestneighbor.h and
+// Uber.h do not compile unmodified); tests/test_ref_textures.py pins the device and the oracle to
+// an independent numpy restatement of the two texture headers and to each other, and the oracle's
+// textured classes over a constant image to the untextured ones that are pinned here
+// (DESIGN.md §4).
 // every standard header the reference pulls in, read before `final` is renamed
 #include <algorithm>
 #include <atomic>

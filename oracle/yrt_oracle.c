@@ -417,12 +417,16 @@ static void tex_get(const Blob* B, int texObj, float px, float py, float out[4])
   if (!strcasecmp(t->type, "bilinear")) {
     const float u = s1 * W - .5f, v = t1 * H - .5f;
     int x = (int)floorf(u), y = (int)floorf(v);
-    x = x < 0 ? 0 : (x > W - 2 ? W - 2 : x);
-    y = y < 0 ? 0 : (y > H - 2 ? H - 2 : y);
+    x = x > W - 2 ? W - 2 : x; x = x < 0 ? 0 : x; /* clamp(x, 0, W - 2) = max(0, min(x, W - 2)) */
+    y = y > H - 2 ? H - 2 : y; y = y < 0 ? 0 : y;
+    /* a defined departure: the reference fetches x + 1, y + 1 unclamped, outside an image that is
+     * 1 texel wide or high (its clamped fetch stands as a comment at Bilinear.h:36-37); x <= W - 2
+     * in every other image, where the clamp changes nothing */
+    const int x1 = x + 1 > W - 1 ? W - 1 : x + 1, y1 = y + 1 > H - 1 ? H - 1 : y + 1;
     const float ur = u - x, vr = v - y, uo = 1.f - ur, vo = 1.f - vr;
     float a[4], b[4], cc[4], d[4];
-    img_get(B, img, x, y, a); img_get(B, img, x + 1, y, b);
-    img_get(B, img, x, y + 1, cc); img_get(B, img, x + 1, y + 1, d);
+    img_get(B, img, x, y, a); img_get(B, img, x1, y, b);
+    img_get(B, img, x, y1, cc); img_get(B, img, x1, y1, d);
     for (int k = 0; k < 4; ++k) c[k] = (a[k] * uo + b[k] * ur) * vo + (cc[k] * uo + d[k] * ur) * vr;
   } else {
     const int si = (int)(s1 * (float)W), ti = (int)(t1 * (float)H);
@@ -2514,6 +2518,13 @@ int oracle_brdf(int kind, const float* args, int n, const float* wo, const float
  * s.xy; out n x 34 = component count, then 3 x (type bits, eval3, sample3, wi3, pdf). */
 int oracle_material_components(const void* blob, size_t bytes, const float* medium4, int n, const float* rows,
                                float* out) {
+  return oracle_material_components_st(blob, bytes, medium4, n, rows, 20, out);
+}
+/* The same on rows of rowWords >= 22 words, words 20 and 21 the hit's texture coordinates dg.s,
+ * dg.t (rowWords 20: both 0); the blob may hold images, textures and a textured material. */
+int oracle_material_components_st(const void* blob, size_t bytes, const float* medium4, int n, const float* rows,
+                                  int rowWords, float* out) {
+  if (rowWords != 20 && rowWords < 22) return fail("rows of 20 or of at least 22 words");
   Blob B;
   if (blob_parse(blob, bytes, &B)) return -1;
   int oi = -1;
@@ -2528,11 +2539,12 @@ int oracle_material_components(const void* blob, size_t bytes, const float* medi
   const Medium cur = {v3(medium4[0], medium4[1], medium4[2]), medium4[3]};
   int rc = 0;
   for (int i = 0; i < n && !rc; ++i) {
-    const float* r = rows + 20 * i;
+    const float* r = rows + (size_t)rowWords * i;
     float* o = out + 34 * i;
     memset(o, 0, 34 * sizeof(float));
     DG dg;
     dg_from(&dg, r + 3, r + 6, r + 9, r + 12);
+    if (rowWords >= 22) { dg.s = r[20]; dg.t = r[21]; }
     const V3 wo = v3(r[0], r[1], r[2]);
     BSet bs;
     shade(&W, &m, cur, &dg, &bs);
@@ -2550,6 +2562,24 @@ int oracle_material_components(const void* blob, size_t bytes, const float* medi
   }
   blob_free(&B);
   return rc;
+}
+
+/* Texture::get of the blob's texture object number `texture` (counting its texture objects in blob
+ * order) at n raw coordinates st (n x 2): RGBA (n x 4). */
+int oracle_texture_get(const void* blob, size_t bytes, int texture, int n, const float* st, float* rgba) {
+  Blob B;
+  if (blob_parse(blob, bytes, &B)) return -1;
+  int oi = -1;
+  for (int i = 0, k = 0; i < B.nobj && oi < 0; ++i)
+    if (B.objs[i].kind == K_TEXTURE && k++ == texture) oi = i;
+  const int img = oi < 0 ? -1 : p_obj(&B.objs[oi], "image");
+  if (img < 0 || img >= B.nobj || B.objs[img].kind != K_IMAGE || B.objs[img].imgW < 1 || B.objs[img].imgH < 1) {
+    blob_free(&B);
+    return fail("no such texture, or a texture without an image");
+  }
+  for (int i = 0; i < n; ++i) tex_get(&B, oi, st[2 * i], st[2 * i + 1], rgba + 4 * i);
+  blob_free(&B);
+  return 0;
 }
 
 /* Light::sample of the blob's first light object placed with transform xfm12 (Light::transform),

@@ -123,6 +123,15 @@ int oracle_brdf(int kind, const float* args, int n, const float* wo, const float
  * component's eval at wi, its sample at s, the sampled wi, pdf) */
 int oracle_material_components(const void* blob, size_t bytes, const float* medium4, int n, const float* rows,
                                float* out);
+/* The same on rows of rowWords words (20, or >= 22 with words 20, 21 = the hit's texture
+ * coordinates dg.s, dg.t); the blob may hold images, textures and a textured material. */
+int oracle_material_components_st(const void* blob, size_t bytes, const float* medium4, int n, const float* rows,
+                                  int rowWords, float* out);
+/* Texture::get (Bilinear.h, nearestneighbor.h) of the blob's texture object number `texture`
+ * (counted among its texture objects, in blob order) at raw coordinates st (n x 2): RGBA (n x 4).
+ * Bilinear: the x + 1, y + 1 fetches are clamped into the image (a defined departure where the
+ * reference reads outside an image 1 texel wide or high). */
+int oracle_texture_get(const void* blob, size_t bytes, int texture, int n, const float* st, float* rgba);
 /* Light::sample of the blob's first light object after Light::transform(xfm12), at shade points P
  * (n x 3) with shading normal Ns and samples s (n x 2): L, wi (n x 3), pdf (n) */
 int oracle_light_sample(const void* blob, size_t bytes, const float* xfm12, int n, const float* P, const float* Ns,

@@ -301,6 +301,82 @@ int yrtDebugShade(YRTDevice dev, int mode, YRTHandle object, const float* rows, 
   DEV_END(-1)
 }
 
+int yrtDebugMaterial(YRTDevice dev, YRTHandle scene, YRTHandle primitive, int mode, const char* set,
+                     const float* medium4, const float* rows, int n, float* out) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  if (!D.gpu) throw std::runtime_error("yrtDebugMaterial: host-only device");
+  if ((mode != 0 && mode != 1) || !rows || !out || n < 1 || (mode == 0 && !medium4))
+    throw std::runtime_error("yrtDebugMaterial: invalid arguments");
+  auto S = D.get<SceneObj>(scene, "scene");
+  auto P = D.get<PrimitiveObj>(primitive, "primitive");
+  if (!S || !S->gpu || !P) throw std::runtime_error("yrtDebugMaterial: takes a committed scene and one of its primitives");
+  const GpuScene& G = *S->gpu;
+  // the primitive's geometry among the slots the scene was committed with
+  int geom = -1;
+  for (size_t i = 0; i < G.slotsCommitted.size() && i < G.slotGeom.size() && geom < 0; ++i)
+    if (G.slotsCommitted[i] && G.slotsCommitted[i]->prim == P) geom = G.slotGeom[i];
+  if (geom < 0 || geom >= (int)G.hGeoms.size())
+    throw std::runtime_error("yrtDebugMaterial: the primitive is no shape of the committed scene");
+  const int mat = G.hGeoms[geom].material;
+  if (mat < 0 || mat >= (int)G.hMaterials.size()) throw std::runtime_error("yrtDebugMaterial: the primitive has no material");
+  // every index the kernels follow from the record: the texture ids and their images
+  for (int k = 0; k < 5; ++k) {
+    const int t = G.hMaterials[mat].tex[k];
+    if (t >= (int)G.hTextures.size() || (t >= 0 && (G.hTextures[t].image < 0 || G.hTextures[t].image >= (int)G.hImages.size())))
+      throw std::runtime_error("yrtDebugMaterial: texture id out of range");
+  }
+  const int variant = shade_variant_index(set);
+  if (variant < 0) throw std::runtime_error(std::string("yrtDebugMaterial: unknown material set '") + (set ? set : "") + "'");
+  int medium = 0;
+  if (mode == 0) {  // Medium::operator== compares by value; a medium the scene does not hold equals none of its own
+    medium = (int)G.hMedia.size();
+    for (size_t i = 0; i < G.hMedia.size() && medium == (int)G.hMedia.size(); ++i)
+      if (G.hMedia[i].x == medium4[0] && G.hMedia[i].y == medium4[1] && G.hMedia[i].z == medium4[2] &&
+          G.hMedia[i].w == medium4[3])
+        medium = (int)i;
+  }
+  HIP_CHECK(hipSetDevice(G.device));
+  const int rc = check_material(G.view, mode, variant, G.hMaterials[mat].type, geom, medium, n, rows, out);
+  if (rc == -2) throw std::runtime_error(std::string("yrtDebugMaterial: the material set '") + set + "' does not hold the primitive's material");
+  if (rc != 0) throw std::runtime_error("yrtDebugMaterial: a failed launch");
+  return 0;
+  DEV_END(-1)
+}
+
+int64_t yrtDebugTexturePool(YRTDevice dev, YRTHandle scene, int what, void* buf, size_t bytes) {
+  DEV_GUARD(dev, -1)
+  auto S = dev->d->get<SceneObj>(scene, "scene");
+  if (!S || !S->gpu) throw std::runtime_error("scene not committed");
+  const GpuScene& G = *S->gpu;
+  const bool host = !dev->d->gpu;
+  std::vector<uint32_t> quads;
+  const void* src = nullptr;   // host memory
+  const void* dsrc = nullptr;  // device memory
+  size_t n = 0;
+  switch (what) {
+    case 0: src = G.hImages.data(); n = G.hImages.size() * sizeof(GpuImage); break;
+    case 1: src = G.hTextures.data(); n = G.hTextures.size() * sizeof(GpuTexture); break;
+    case 2: n = G.texelsBytes; if (host) src = G.hTexels.data(); else dsrc = G.texels.p; break;
+    case 3:
+      n = 4 * G.texels8Bytes;
+      if (!host) dsrc = G.texQuads.p;
+      else if (buf && bytes >= n) { quads = build_tex_quads(G.hImages, G.hTexels, G.texels8Bytes); src = quads.data(); }
+      break;
+    default: throw std::runtime_error("yrtDebugTexturePool: what 0..3");
+  }
+  if (buf && bytes >= n && n) {
+    if (dsrc) {
+      HIP_CHECK(hipSetDevice(G.device));
+      HIP_CHECK(hipMemcpy(buf, dsrc, n, hipMemcpyDeviceToHost));
+    } else {
+      memcpy(buf, src, n);
+    }
+  }
+  return (int64_t)n;
+  DEV_END(-1)
+}
+
 int yrtDebugTileScatter(int t, int T) {
   if (T < 1 || t < 0 || t >= T) return -1;
   return yrt_tile_scatter(t, T);

@@ -69,6 +69,34 @@ GpuLight gpu_light_record(const LightInst& L) {
   return g;
 }
 
+// Bilinear footprints of the 8-bit images (kernels/yrt_shade.h tex_get_rec): record i of an image,
+// i = y W + x, holds the 4-byte texels (x, y), (x', y), (x, y'), (x', y') with x' = min(x + 1, W - 1)
+// and y' = min(y + 1, H - 1), at 4x the texel's byte offset: the bytes the four row-major fetches
+// read, of its own image only. Float images keep the row-major pool only.
+std::vector<uint32_t> build_tex_quads(const std::vector<GpuImage>& images, const std::vector<uint8_t>& texels,
+                                      size_t texels8Bytes) {
+  std::vector<uint32_t> quads(texels8Bytes, 0u);
+  for (const GpuImage& g : images) {
+    if (g.format == IMG_RGBAF32) continue;
+    const size_t W = (size_t)g.width, H = (size_t)g.height;
+    auto word = [&](size_t x, size_t y) -> uint32_t {
+      uint32_t w;
+      memcpy(&w, &texels[(size_t)g.offset + 4 * (y * W + x)], 4);
+      return w;
+    };
+    for (size_t y = 0; y < H; ++y)
+      for (size_t x = 0; x < W; ++x) {
+        const size_t q = (size_t)g.offset + 4 * (y * W + x);  // uint32 index of the record = byte offset
+        const size_t x1 = std::min(x + 1, W - 1), y1 = std::min(y + 1, H - 1);
+        quads[q + 0] = word(x, y);
+        quads[q + 1] = word(x1, y);
+        quads[q + 2] = word(x, y1);
+        quads[q + 3] = word(x1, y1);
+      }
+  }
+  return quads;
+}
+
 std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<ScenePrim>>& prims, int stackDepth,
                                           bool upload, bool morton, hipStream_t stream, bool timing) {
   auto t0 = std::chrono::steady_clock::now();
@@ -311,16 +339,6 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
       S->bboxHi[k] = std::max(S->bboxHi[k], triVerts[i + k]);
     }
 
-  if (!upload) {
-    S->hNodes = std::move(bvh.nodes);
-    S->hQNodes = std::move(qnodes);
-    S->hTris = std::move(bvh.tris);
-    S->hGeoms = geoms;
-    S->hTriGeom = triGeom;
-    S->view.numLights = (int)lights.size();
-    S->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return S;
-  }
   {
     // place the float images after the 8-bit ones; image and texture records get final offsets
     const size_t base = (texels.size() + 15) & ~size_t(15);
@@ -330,6 +348,22 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
     for (GpuImage& g : images)
       if (g.format == IMG_RGBAF32) g.offset += (int64_t)base;
     for (GpuTexture& t : textures) t.offset = images[t.image].offset;
+  }
+  S->texelsBytes = texels.size();
+  S->hMaterials = materials;
+  S->hTextures = textures;
+  S->hImages = images;
+  S->hMedia = media;
+  if (!upload) {
+    S->hTexels = std::move(texels);  // a host-only scene's pool (yrtDebugTexturePool)
+    S->hNodes = std::move(bvh.nodes);
+    S->hQNodes = std::move(qnodes);
+    S->hTris = std::move(bvh.tris);
+    S->hGeoms = geoms;
+    S->hTriGeom = triGeom;
+    S->view.numLights = (int)lights.size();
+    S->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return S;
   }
   for (const GpuMaterial& m : materials) S->materialMask |= 1u << m.type;
   for (const GpuLight& l : lights) S->materialMask |= 1u << (16 + l.type);  // light_bit (kernels/yrt_shade.h)
@@ -397,29 +431,7 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
   S->textures.upload(textures);
   S->images.upload(images);
   S->texels.upload(texels);
-  {
-    // bilinear footprints of the 8-bit images (kernels/yrt_shade.h tex_get): record i of an image
-    // holds the 4-byte texels i, i+1, i+W, i+W+1 — the bytes the four row-major fetches read —
-    // at 4x the texel's byte offset; float images keep the row-major pool only
-    std::vector<uint32_t> quads(S->texels8Bytes, 0u);
-    auto word = [&](size_t b) -> uint32_t {
-      uint32_t w = 0;
-      if (b + 4 <= S->texels8Bytes) memcpy(&w, &texels[b], 4);
-      return w;
-    };
-    for (const GpuImage& g : images) {
-      if (g.format == IMG_RGBAF32) continue;
-      const size_t n = (size_t)g.width * g.height, W = (size_t)g.width;
-      for (size_t i = 0; i < n; ++i) {
-        const size_t b = (size_t)g.offset + 4 * i, q = b;  // uint32 index of the record = byte offset
-        quads[q + 0] = word(b);
-        quads[q + 1] = word(b + 4);
-        quads[q + 2] = word(b + 4 * W);
-        quads[q + 3] = word(b + 4 * W + 4);
-      }
-    }
-    S->texQuads.upload(quads);
-  }
+  S->texQuads.upload(build_tex_quads(images, texels, S->texels8Bytes));
   S->lights.upload(lights);
   S->hLights = lights;
   S->hEnvLights = envLights;
@@ -523,6 +535,7 @@ std::shared_ptr<GpuScene> replicate_gpu_scene(const GpuScene& src, int device) {
   R->bvhDepth = src.bvhDepth;
   R->refits = src.refits;
   R->texels8Bytes = src.texels8Bytes;
+  R->texelsBytes = src.texelsBytes;
   return R;
 }
 

@@ -65,6 +65,14 @@ struct GpuScene {
   SceneView view{};
   unsigned materialMask = 0;  // bit MAT_x per material type, bit 16+LIGHT_x per light type used (shade kernel variant)
   size_t texels8Bytes = 0;    // the 8-bit images' part of the texel pool (float images follow it)
+  size_t texelsBytes = 0;     // the whole pool
+  // host mirrors of the small shading tables (the debug probes' bounds checks and pool export);
+  // hTexels: the texel pool of a host-only scene, which has no device copy
+  std::vector<GpuMaterial> hMaterials;
+  std::vector<GpuTexture> hTextures;
+  std::vector<GpuImage> hImages;
+  std::vector<float4> hMedia;
+  std::vector<uint8_t> hTexels;
   // host mirrors (BVH export, precomputed light sampling, stats)
   std::vector<GpuNode> hNodes;
   std::vector<GpuQNode> hQNodes;  // the same tree with 64-B quantized nodes (common/yrt_qnode.h)
@@ -93,6 +101,11 @@ struct GpuScene {
 // The device record of a world-space light without the scene's own indices (image, precomputed
 // slot): what the light samplers read. build_gpu_scene fills those in.
 GpuLight gpu_light_record(const LightInst& L);
+
+// The 2x2 footprint records of the pool's 8-bit images (texQuads): one 16-byte record per texel,
+// 4 x texels8Bytes in all, as uint32 words.
+std::vector<uint32_t> build_tex_quads(const std::vector<GpuImage>& images, const std::vector<uint8_t>& texels,
+                                      size_t texels8Bytes);
 
 // morton: the scene builder "morton" (bvh_build.h) instead of the host SAH builder: on the GPU in
 // `stream` when the scene is uploaded, else its host loop; timing: HIP-event time of its kernels

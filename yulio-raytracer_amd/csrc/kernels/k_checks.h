@@ -154,4 +154,102 @@ __global__ __launch_bounds__(64) void k_check_shade(int mode, int n, const float
   if (mode == 2) o[6] = o[7] = o[8] = o[9] = o[10] = o[11] = 0.f;
 }
 
+// ---------------------------------------------------------------- material probe
+// k_check_material<MM> (yrtDebugMaterial mode 0, test-only): Material::shade of one geometry of a
+// committed scene as k_shade<MM> performs it, one thread per row: the geometry's record through
+// geom_burst<MM>, shade_material<MM> on the row's dg, then comp_eval and comp_sample of every
+// component it created (after shade_material: Obj's bump map has turned dg.Ns by then). It holds
+// no formula of its own; the pieces of the record that MM's burst leaves out stay zero, as in
+// k_shade.
+//   rows  n x 22 words: wo, Ns, Ng, Tx, Ty, wi (3 each), s.xy, then dg.s, dg.t
+//   out   n x 34 words: the component count, then 3 x (comp_type(kind), eval3, sample3, wi3, pdf),
+//         zero beyond the count (oracle/ref_shade.cpp's ref_material_components)
+// medium: the current medium's index in the scene's medium table.
+#define YRT_MAT_ROW 22
+#define YRT_MAT_OUT 34
+template <unsigned MM>
+__global__ __launch_bounds__(64) void k_check_material(SceneView sv, int geom, int medium, int n,
+                                                       const float* __restrict__ rows, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr unsigned CM = comps_of(MM);
+  const float* r = rows + (size_t)i * YRT_MAT_ROW;
+  float* o = out + (size_t)i * YRT_MAT_OUT;
+  GeomHead gh;
+  GpuMaterial gm = {};
+  GpuTexture gt0 = {};
+  geom_burst<MM>(sv.geomRecs + geom, gh, gm, gt0);
+  const V3 wo = v3(r[0], r[1], r[2]), wi = v3(r[15], r[16], r[17]);
+  DG dg;
+  dg.P = v3s(0.f);
+  dg.Ns = v3(r[3], r[4], r[5]);
+  dg.Ng = v3(r[6], r[7], r[8]);
+  dg.Tx = v3(r[9], r[10], r[11]);
+  dg.Ty = v3(r[12], r[13], r[14]);
+  dg.s = r[20];
+  dg.t = r[21];
+  dg.error = 0.f;
+  dg.material = gh.material;
+  dg.light = -1;
+  dg.illumMask = dg.shadowMask = -1;
+  BRDFSet bs;
+  bs.n = 0;
+#pragma unroll
+  for (int k = 0; k < YRT_MAX_COMPS; ++k) {
+    bs.c[k].kind = 0;
+    bs.c[k].R = v3s(0.f);
+    bs.c[k].a = bs.c[k].b = bs.c[k].c = 0.f;
+  }
+  if (dg.material >= 0) shade_material<MM>(sv, gm, gt0, dg.material, medium, dg, bs);
+  dg_frame(dg);
+  const float4 sd = sample_dir(r[18], r[19]);
+  o[0] = __int_as_float(bs.n);
+#pragma unroll
+  for (int k = 0; k < YRT_MAX_COMPS; ++k) {
+    float* c = o + 1 + 11 * k;
+    V3 e = v3s(0.f), sa = v3s(0.f), w = v3s(0.f);
+    float pdf = 0.f;
+    uint32_t type = 0;
+    if (k < bs.n) {
+      type = comp_type(bs.c[k].kind);
+      e = comp_eval<CM>(bs.c[k], sv.materials, wo, dg, wi);
+      sa = comp_sample<CM>(bs.c[k], sv.materials, wo, dg, sd, r[19], w, pdf);
+    }
+    c[0] = __uint_as_float(type);
+    c[1] = e.x; c[2] = e.y; c[3] = e.z;
+    c[4] = sa.x; c[5] = sa.y; c[6] = sa.z;
+    c[7] = w.x; c[8] = w.y; c[9] = w.z;
+    c[10] = pdf;
+  }
+}
+
+// k_check_textures (yrtDebugMaterial mode 1, test-only): the texture lookups of one geometry's
+// material at raw (s, t), one thread per row; the material's s0 / ds are not applied.
+//   st   n x 2 words
+//   out  n x 24 words: RGBA of tex_get(m.tex[k]) for k = 0..4 (zero where m.tex[k] < 0), then RGBA of
+//        tex_get_rec over the descriptor copy GpuGeomRec::t0 as geom_burst hands it to k_shade
+//        (zero where m.tex[0] < 0)
+#define YRT_TEX_OUT 24
+__global__ __launch_bounds__(64) void k_check_textures(SceneView sv, int geom, int n, const float* __restrict__ st,
+                                                       float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float s = st[2 * i], t = st[2 * i + 1];
+  float* o = out + (size_t)i * YRT_TEX_OUT;
+  GeomHead gh;
+  GpuMaterial gm = {};
+  GpuTexture gt0 = {};
+  geom_burst<YRT_ALL_MATS>(sv.geomRecs + geom, gh, gm, gt0);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    float c[4] = {0.f, 0.f, 0.f, 0.f};
+    if (k < 5) {
+      if (gm.tex[k] >= 0) tex_get(sv.textures, sv.images, sv.texels, sv.texQuads, gm.tex[k], s, t, c);
+    } else if (gm.tex[0] >= 0) {
+      tex_get_rec(gt0, sv.texels, sv.texQuads, s, t, c);
+    }
+    o[4 * k] = c[0]; o[4 * k + 1] = c[1]; o[4 * k + 2] = c[2]; o[4 * k + 3] = c[3];
+  }
+}
+
 }  // namespace yrt

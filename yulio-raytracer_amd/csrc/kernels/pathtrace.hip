@@ -253,6 +253,53 @@ int check_shade(int mode, int n, const float* rows, const GpuMaterial* mats, int
   return rc;
 }
 
+// the names yrtDebugMaterial's caller gives kShadeVariants' sets, in their order
+static const char* const kShadeVariantNames[] = {"uber", "obj", "spheres", "stereo", "collada", "all"};
+
+int shade_variant_index(const char* name) {
+  for (int i = 0; i < (int)(sizeof(kShadeVariants) / sizeof(kShadeVariants[0])); ++i)
+    if (name && !strcmp(name, kShadeVariantNames[i])) return i;
+  return -1;
+}
+
+template <unsigned MM>
+static void launch_check_material_t(const SceneView& sv, int geom, int medium, int n, const float* rows, float* out) {
+  hipLaunchKernelGGL(k_check_material<MM>, dim3((n + 63) / 64), dim3(64), 0, 0, sv, geom, medium, n, rows, out);
+}
+
+int check_material(const SceneView& sv, int mode, int variant, int matType, int geom, int medium, int n,
+                   const float* rows, float* out) {
+  if ((mode != 0 && mode != 1) || n < 1 || !rows || !out || geom < 0) return -1;
+  if (variant < 0 || variant >= (int)(sizeof(kShadeVariants) / sizeof(kShadeVariants[0]))) return -1;
+  // a material outside the named set is not launched: its case is not compiled into that instantiation
+  if (mode == 0 && (matType < 1 || matType > 31 || !(kShadeVariants[variant] & mat_bit(matType)))) return -2;
+  const size_t rowBytes = (size_t)n * (mode == 0 ? YRT_MAT_ROW : 2) * sizeof(float);
+  const size_t outBytes = (size_t)n * (mode == 0 ? YRT_MAT_OUT : YRT_TEX_OUT) * sizeof(float);
+  float *dRows = nullptr, *dOut = nullptr;
+  int rc = 0;
+  if (hipMalloc(&dRows, rowBytes) != hipSuccess || hipMalloc(&dOut, outBytes) != hipSuccess) rc = -1;
+  if (!rc && hipMemcpy(dRows, rows, rowBytes, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
+  if (!rc) {
+    if (mode == 1) {
+      hipLaunchKernelGGL(k_check_textures, dim3((n + 63) / 64), dim3(64), 0, 0, sv, geom, n, dRows, dOut);
+    } else {
+      switch (kShadeVariants[variant]) {
+        case YRT_SV_UBER: launch_check_material_t<YRT_SV_UBER>(sv, geom, medium, n, dRows, dOut); break;
+        case YRT_SV_OBJ: launch_check_material_t<YRT_SV_OBJ>(sv, geom, medium, n, dRows, dOut); break;
+        case YRT_SV_SPHERES: launch_check_material_t<YRT_SV_SPHERES>(sv, geom, medium, n, dRows, dOut); break;
+        case YRT_SV_STEREO: launch_check_material_t<YRT_SV_STEREO>(sv, geom, medium, n, dRows, dOut); break;
+        case YRT_SV_COLLADA: launch_check_material_t<YRT_SV_COLLADA>(sv, geom, medium, n, dRows, dOut); break;
+        default: launch_check_material_t<YRT_SV_ALL>(sv, geom, medium, n, dRows, dOut); break;
+      }
+    }
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = -1;
+  }
+  (void)hipFree(dOut);
+  (void)hipFree(dRows);
+  return rc;
+}
+
 int check_dir_terms(int mode, int n, const float* u, const float* v, float* out4) {
   if ((mode != 0 && mode != 1) || n < 1 || !u || !v || !out4) return -1;
   float* dIn = nullptr;  // the u row, then the v row

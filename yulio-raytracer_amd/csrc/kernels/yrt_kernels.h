@@ -28,7 +28,8 @@ struct SceneView {
   const GpuTexture* textures;
   const GpuImage* images;
   const uint8_t* texels;
-  const uint8_t* texQuads;  // per 8-bit texel i: texels i, i+1, i+W, i+W+1 (16 B at 4x its texel offset)
+  const uint8_t* texQuads;  // per 8-bit texel (x, y): texels (x, y), (x', y), (x, y'), (x', y'), x' = min(x + 1, W - 1)
+                            // (16 B at 4x its texel offset)
   const GpuLight* lights;
   const int* envLights;
   const int* directLights;  // the lights whose samples can carry radiance (Device::render), in light order
@@ -199,6 +200,15 @@ int check_math_table(int fn, const uint16_t* table2048, unsigned long long* host
 // host pointers; mats numMats records (may be null), cam / light one host record for modes 2 / 3
 int check_shade(int mode, int n, const float* rows, const GpuMaterial* mats, int numMats, const GpuCamera* cam,
                 const GpuLight* light, float* out);
+// Material probe (k_check_material / k_check_textures, k_checks.h; test-only) on geometry `geom` of
+// an uploaded scene, host rows in and out. variant: the index of one of launch_shade's material
+// sets (shade_variant_index: "uber", "obj", "spheres", "stereo", "collada", "all"; -1 unknown).
+// mode 0: n rows of 22 words -> 34 words through that set's instantiation, medium the current
+// medium's table index; -2 without a launch when the set does not hold matType. mode 1: n rows
+// (s, t) -> 24 words. The caller has checked geom and the material's texture ids.
+int shade_variant_index(const char* name);
+int check_material(const SceneView& sv, int mode, int variant, int matType, int geom, int medium, int n,
+                   const float* rows, float* out);
 // Direction-term probe (k_sample_dirs.h; test-only): the terms of n samples (u[i], v[i]) into
 // out4 (n x 4 floats), host pointers. mode 0: spelled out per sample (k_check_dir_terms);
 // mode 1: k_sample_dirs over the samples as one slot of n records

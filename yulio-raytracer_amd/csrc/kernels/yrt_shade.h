@@ -237,10 +237,13 @@ __device__ __forceinline__ void tex_get_rec(const GpuTexture& tx, const uint8_t*
       texel_u8(qd.z, rgb, c01);
       texel_u8(qd.w, rgb, c11);
     } else {
+      // the +1 fetches stay inside the image when it is 1 texel wide or high (the quad records
+      // hold the same clamp); x <= W - 2 otherwise, so nothing changes there
+      const int x1 = min(x + 1, im.width - 1), y1 = min(y + 1, im.height - 1);
       texel(im, pool, x, y, c00);
-      texel(im, pool, x + 1, y, c10);
-      texel(im, pool, x, y + 1, c01);
-      texel(im, pool, x + 1, y + 1, c11);
+      texel(im, pool, x1, y, c10);
+      texel(im, pool, x, y1, c01);
+      texel(im, pool, x1, y1, c11);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k)

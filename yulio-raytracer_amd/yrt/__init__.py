@@ -245,6 +245,50 @@ class Device:
                                      out.ctypes.data), "yrtDebugShade")
         return out
 
+    def debug_material(self, scene, prim, rows, medium=(1.0, 1.0, 1.0, 1.0), set="all"):
+        """yrtDebugMaterial mode 0, the test-only probe of Material::shade on the device: rows float32
+        (n, 22) = wo, Ns, Ng, Tx, Ty, wi, s.xy, dg.s, dg.t on primitive `prim` of the committed
+        `scene`, in the medium (T.rgb, eta), through the shade kernel's material set `set` ("uber",
+        "obj", "spheres", "stereo", "collada", "all"). Returns float32 (n, 34) = count, then 3 x
+        (type bits, eval3, sample3, wi3, pdf)."""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 22)
+        med = np.ascontiguousarray(medium, np.float32).reshape(4)
+        out = np.zeros((rows.shape[0], 34), np.float32)
+        self._rc(N.dev.yrtDebugMaterial(self.h, scene, prim, 0, _b(set), med.ctypes.data, rows.ctypes.data,
+                                        rows.shape[0], out.ctypes.data), "yrtDebugMaterial")
+        return out
+
+    def debug_textures(self, scene, prim, st):
+        """yrtDebugMaterial mode 1: the lookups of `prim`'s material's textures at raw st float32
+        (n, 2). Returns float32 (n, 6, 4): RGBA through texture slots 0..4 (zero where unset), then
+        slot 0 through the descriptor copy in the geometry record."""
+        st = np.ascontiguousarray(st, np.float32).reshape(-1, 2)
+        out = np.zeros((st.shape[0], 6, 4), np.float32)
+        self._rc(N.dev.yrtDebugMaterial(self.h, scene, prim, 1, b"all", None, st.ctypes.data, st.shape[0],
+                                        out.ctypes.data), "yrtDebugMaterial")
+        return out
+
+    def debug_texture_pools(self, scene) -> dict:
+        """yrtDebugTexturePool: the committed scene's texture tables as the kernels read them:
+        images int32 (n, 6) = width, height, format, pad, pool offset (low, high word), textures
+        int32 (n, 8) = image, filter, invert, width, height, format, offset (low, high), texels
+        uint8 (the row-major pool, 8-bit images first), quads uint32 (records, 4): the 2x2 footprint
+        record of every texel of the pool's 8-bit part."""
+        out = {}
+        for what, (name, dtype) in enumerate((("images", np.int32), ("textures", np.int32), ("texels", np.uint8),
+                                              ("quads", np.uint32))):
+            n = N.dev.yrtDebugTexturePool(self.h, scene, what, None, 0)
+            if n < 0:
+                raise RuntimeError(f"yrtDebugTexturePool: {self.error()}")
+            buf = np.zeros(n // np.dtype(dtype).itemsize, dtype)
+            if N.dev.yrtDebugTexturePool(self.h, scene, what, buf.ctypes.data, buf.nbytes) != n:
+                raise RuntimeError(f"yrtDebugTexturePool: {self.error()}")
+            out[name] = buf
+        out["images"] = out["images"].reshape(-1, 6)
+        out["textures"] = out["textures"].reshape(-1, 8)
+        out["quads"] = out["quads"].reshape(-1, 4)
+        return out
+
     def debug_sample_dirs(self, spp, sets, iteration, num1D, num2D, filter="bspline"):
         """yrtDebugSampleDirs: the request's frame cache entry as a render creates it. Returns its
         sample table, float32 (dims, records), and its direction-term table read back from the

@@ -203,6 +203,11 @@ try:  # the shading-layer probe; absent from older builds selected with YRT_LIB_
     _sig(dev, "yrtDebugShade", i32, vp, i32, vp, vp, i32, vp, i32, vp)
 except AttributeError:
     pass
+try:  # the material and texture probes; absent from older builds selected with YRT_LIB_DIR
+    _sig(dev, "yrtDebugMaterial", i32, vp, vp, vp, i32, cstr, vp, vp, i32, vp)
+    _sig(dev, "yrtDebugTexturePool", C.c_int64, vp, vp, i32, vp, sz)
+except AttributeError:
+    pass
 try:  # the direction-term table's probes; absent from older builds selected with YRT_LIB_DIR
     _sig(dev, "yrtDebugSampleDirs", i32, vp, i32, i32, i32, i32, i32, cstr, PF, sz, PF, sz)
     _sig(dev, "yrtDebugDirTerms", i32, vp, i32, PF, PF, i32, PF)
