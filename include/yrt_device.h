@@ -182,8 +182,24 @@ YRT_API int yrtDenoiseDefaults(YRTDenoiseParams* p);
  * gathered frame (rank 0): it filters whatever the framebuffer holds. p = NULL: defaults. */
 YRT_API int yrtDenoiseFrameBuffer(YRTDevice dev, YRTHandle camera, YRTHandle scene, YRTHandle framebuffer,
                                   const YRTDenoiseParams* p);
+/* The same filter over a stereo cube as one surface: a tap that leaves a face reads the pixel its
+ * direction falls on on the neighbouring face of the same eye (corner taps stay skipped, the eyes
+ * never exchange taps), so the cube's edges are filtered like its faces' interiors. numFrames is 6
+ * (one eye) or 12; every camera is a committed "stereo" camera, the faces cubeFaceIndex % 6 of each
+ * eye (cubeFaceIndex / 6) each present exactly once, in any order, the cameras of one eye equal in
+ * everything but cubeFaceIndex; framebuffers[k] holds the frame rendered through cameras[k], all
+ * square, of one size (at most 16384) and one format. The cameras must form an ideal cube (what a
+ * lookAt perpendicular to `up` gives); otherwise the call fails and writes nothing. p is read as
+ * by yrtDenoiseFrameBuffer, and each frame is filtered where it lives, by that call's rules. */
+YRT_API int yrtDenoiseCube(YRTDevice dev, const YRTHandle* cameras, int numFrames, YRTHandle scene,
+                           const YRTHandle* framebuffers, const YRTDenoiseParams* p);
+/* Host-side: the rule that says where a cube filter tap lands (csrc/common/yrt_cube_tap.h). The
+ * tap (qx, qy) of face `face` (0..5 within its eye) of W x W faces: returns 1 and (g, x', y') for
+ * a tap that lands on a face, 0 for a skipped corner tap, -1 for arguments out of range (W outside
+ * 1..16384, a tap farther than 2^17 pixels from the face, a null pointer). */
+YRT_API int yrtDebugCubeTap(int W, int face, int qx, int qy, int* g, int* x, int* y);
 /* With yrtSetKernelTiming on: HIP-event times, in ms, of the kernels of the last guide pass
- * (yrtRenderGuides, yrtRenderAlbedo, or the one inside yrtDenoiseFrameBuffer, which renders the
+ * (yrtRenderGuides, yrtRenderAlbedo, or the one inside yrtDenoiseFrameBuffer / yrtDenoiseCube, which renders the
  * albedo in the same kernel when demodulate is set) and of the last filter (its load and
  * iterations, without the guide pass and any host copy). Either pointer may be NULL. */
 YRT_API int yrtGetDenoiseTimes(YRTDevice dev, float* msGuides, float* msFilter);

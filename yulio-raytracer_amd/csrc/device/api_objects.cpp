@@ -4,6 +4,7 @@
 // (device_singleray/api/singleray_device.cpp:99-709).
 #include <strings.h>
 
+#include "../common/yrt_cube_tap.h"
 #include "device.h"
 #include "image_io.h"
 
@@ -763,6 +764,73 @@ int yrtDenoiseFrameBuffer(YRTDevice dev, YRTHandle camera, YRTHandle scene, YRTH
   auto F = D.get<FrameBufferObj>(framebuffer, "framebuffer");
   if (!C || !S || !F) throw std::runtime_error("yrtDenoiseFrameBuffer: null handle");
   D.denoise(*C, *S, *F, dp);
+  return 0;
+  DEV_END(-1)
+}
+
+// Validation first (it needs no GPU), then the host-only refusal, then the filter. The slots are
+// ordered eye-major, face-minor: slot = eye * 6 + cubeFaceIndex % 6 (one eye: slots 0..5).
+int yrtDenoiseCube(YRTDevice dev, const YRTHandle* cameras, int numFrames, YRTHandle scene,
+                   const YRTHandle* framebuffers, const YRTDenoiseParams* p) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  const YRTDenoiseParams dp = denoise_params(p);
+  if (numFrames != 6 && numFrames != 12)
+    throw std::runtime_error("yrtDenoiseCube: numFrames must be 6 (one eye) or 12, got " + std::to_string(numFrames));
+  if (!cameras || !framebuffers) throw std::runtime_error("yrtDenoiseCube: null camera or framebuffer array");
+  auto S = D.get<SceneObj>(scene, "scene");
+  if (!S) throw std::runtime_error("yrtDenoiseCube: null handle");
+  std::vector<std::shared_ptr<CameraObj>> camRefs(numFrames);
+  std::vector<std::shared_ptr<FrameBufferObj>> fbRefs(numFrames);
+  std::vector<CameraObj*> C(numFrames, nullptr);
+  std::vector<FrameBufferObj*> F(numFrames, nullptr);
+  int firstEye = -1;
+  for (int k = 0; k < numFrames; ++k) {
+    camRefs[k] = D.get<CameraObj>(cameras[k], "camera");
+    fbRefs[k] = D.get<FrameBufferObj>(framebuffers[k], "framebuffer");
+    if (!camRefs[k] || !fbRefs[k]) throw std::runtime_error("yrtDenoiseCube: null handle");
+    const GpuCamera& cam = camRefs[k]->cam;
+    if (!ieq(camRefs[k]->type.c_str(), "stereo") || cam.type != CAM_STEREO)
+      throw std::runtime_error("yrtDenoiseCube: camera " + std::to_string(k) + " is not a committed \"stereo\" camera");
+    if (cam.cubeFaceIndex < 0 || cam.cubeFaceIndex > 11)
+      throw std::runtime_error("yrtDenoiseCube: camera " + std::to_string(k) + " has a cubeFaceIndex outside 0..11");
+    const int eye = cam.cubeFaceIndex / 6, face = cam.cubeFaceIndex % 6;
+    if (firstEye < 0) firstEye = eye;
+    if (numFrames == 6 && eye != firstEye)
+      throw std::runtime_error("yrtDenoiseCube: 6 frames must be the six faces of one eye; camera " + std::to_string(k) +
+                               " belongs to the other eye, so a face is missing");
+    const int slot = (numFrames == 6 ? 0 : eye * 6) + face;
+    if (C[slot])
+      throw std::runtime_error("yrtDenoiseCube: face " + std::to_string(face) + " of the " + (eye ? "right" : "left") +
+                               " eye appears twice, so another face is missing");
+    C[slot] = camRefs[k].get();
+    F[slot] = fbRefs[k].get();
+  }
+  for (int e = 0; e < numFrames / 6; ++e) {
+    GpuCamera first = C[6 * e]->cam;
+    first.cubeFaceIndex = 0;
+    for (int f = 1; f < 6; ++f) {
+      GpuCamera other = C[6 * e + f]->cam;
+      other.cubeFaceIndex = 0;
+      if (memcmp(&first, &other, sizeof(GpuCamera)) != 0)
+        throw std::runtime_error("yrtDenoiseCube: the cameras of one eye differ in more than cubeFaceIndex (face " +
+                                 std::to_string(f) + " against face 0)");
+    }
+    const std::string defect = cube_cameras_defect(C[6 * e]->cam);
+    if (!defect.empty()) throw std::runtime_error("yrtDenoiseCube: " + defect);
+  }
+  const int W = F[0]->width;
+  for (int k = 0; k < numFrames; ++k) {
+    if (F[k]->width != F[k]->height || F[k]->width < 1)
+      throw std::runtime_error("yrtDenoiseCube: a cube face's framebuffer must be square");
+    if (F[k]->width != W || F[k]->format != F[0]->format)
+      throw std::runtime_error("yrtDenoiseCube: the framebuffers must have one size and one format");
+    for (int j = 0; j < k; ++j)
+      if (F[j] == F[k]) throw std::runtime_error("yrtDenoiseCube: a framebuffer appears twice");
+  }
+  if (W > YRT_CUBE_MAX_WIDTH) throw std::runtime_error("yrtDenoiseCube: faces wider than 16384 pixels");
+  if (!D.gpu) throw std::runtime_error("yrtDenoiseCube: host-only device (created with parms \"host\")");
+  D.denoiseCube(C, *S, F, dp);
   return 0;
   DEV_END(-1)
 }

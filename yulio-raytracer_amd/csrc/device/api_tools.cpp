@@ -3,6 +3,7 @@
 // the shard communicator and the in-process hub.
 #include <strings.h>
 
+#include "../common/yrt_cube_tap.h"
 #include "../common/yrt_tile_scatter.h"
 #include "device.h"
 #include "image_io.h"
@@ -380,6 +381,11 @@ int64_t yrtDebugTexturePool(YRTDevice dev, YRTHandle scene, int what, void* buf,
 int yrtDebugTileScatter(int t, int T) {
   if (T < 1 || t < 0 || t >= T) return -1;
   return yrt_tile_scatter(t, T);
+}
+
+int yrtDebugCubeTap(int W, int face, int qx, int qy, int* g, int* x, int* y) {
+  if (!g || !x || !y) return -1;
+  return yrt_cube_tap(W, face, qx, qy, g, x, y);
 }
 
 int yrtDebugBatchPlan(int64_t shardTiles, int spp, int64_t capacity, int lanes, int capture, int grow, int64_t* out4) {

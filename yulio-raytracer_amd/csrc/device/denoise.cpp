@@ -1,6 +1,6 @@
 // denoise.cpp — the denoise stage of the device plugin: the first-hit guide pass (yrtRenderGuides,
 // yrtRenderAlbedo) and the edge-avoiding a-trous filter over a rendered frame
-// (yrtDenoiseFrameBuffer).
+// (yrtDenoiseFrameBuffer) or over the faces of a stereo cube as one surface (yrtDenoiseCube).
 #include "device.h"
 
 namespace yrt {
@@ -25,6 +25,27 @@ void Device::guides(CameraObj& C, SceneObj& S, int W, int H, const char* what, b
   HIP_CHECK(hipGetLastError());
 }
 
+// Buffer `id` of F as the filter reads and writes it. A frame still pending in this device's frame
+// block in the block's own layout (RGB8, RGB_FLOAT32) is filtered there: io.pixels points into the
+// block. Any other frame is read back first if it is pending and then lives in F.buffer(id):
+// io.pixels is null and the caller uploads it.
+Device::FilterFrame Device::filter_frame(FrameBufferObj& F, int id) {
+  const bool bytes8 = F.format == FB_RGB8 || F.format == FB_RGBA8;
+  const bool rgba = F.format == FB_RGBA8 || F.format == FB_RGBA_FLOAT32;
+  FilterFrame ff;
+  ff.io.pixels = nullptr;
+  ff.io.width = F.width;
+  ff.io.height = F.height;
+  ff.io.pixStride = rgba ? 4 : 3;
+  ff.io.bytes = bytes8 ? 1 : 0;
+  ff.io.rowStride = bytes8 ? F.stride : F.stride / sizeof(float);
+  const bool pending = id < (int)F.pending.size() && F.pending[id].keep;
+  ff.inBlock = pending && !rgba && F.pending[id].hipDevice == hipDevice;
+  if (ff.inBlock) ff.io.pixels = const_cast<void*>(F.pending[id].src);
+  else if (pending) fb_read_back(F, id);
+  return ff;
+}
+
 // yrtDenoiseFrameBuffer: guides, c_0 = the frame as it stands, `iterations` a-trous passes
 // ping-ponging between two float4 frames, the last one storing into the frame's own format.
 // An RGB8 / RGB_FLOAT32 frame still in ctx[0]'s frame block is filtered there (the block holds
@@ -43,21 +64,11 @@ void Device::denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDeno
   const bool demod = p.demodulate != 0;
   guides(C, S, W, H, "yrtDenoiseFrameBuffer", demod);
   GpuCtx& g = *ctx[0];
-  const bool bytes8 = F.format == FB_RGB8 || F.format == FB_RGBA8;
-  const bool rgba = F.format == FB_RGBA8 || F.format == FB_RGBA_FLOAT32;
-  FrameIO io;
-  io.width = W;
-  io.height = H;
-  io.pixStride = rgba ? 4 : 3;
-  io.bytes = bytes8 ? 1 : 0;
-  io.rowStride = bytes8 ? F.stride : F.stride / sizeof(float);
-  const bool pending = id < (int)F.pending.size() && F.pending[id].keep;
-  const bool inBlock = pending && !rgba && F.pending[id].hipDevice == hipDevice;
+  const FilterFrame ff = filter_frame(F, id);
+  const bool inBlock = ff.inBlock;
   const size_t fbBytes = F.stride * (size_t)H;
-  if (inBlock) {
-    io.pixels = const_cast<void*>(F.pending[id].src);
-  } else {
-    if (pending) fb_read_back(F, id);
+  FrameIO io = ff.io;
+  if (!inBlock) {
     HIP_CHECK(hipSetDevice(hipDevice));
     g.dFilterFb.alloc(fbBytes);
     HIP_CHECK(hipMemcpyAsync(g.dFilterFb.p, F.buffer(id), fbBytes, hipMemcpyHostToDevice, stream));
@@ -95,6 +106,166 @@ void Device::denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDeno
   });
   HIP_CHECK(hipGetLastError());
   if (!inBlock) HIP_CHECK(hipMemcpyAsync(F.buffer(id), g.dFilterFb.p, fbBytes, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  evGuides.read(msGuides);
+  evFilter.read(msFilter);
+}
+
+// The ideal cube's rotation of face 0 that gives face f, in face 0's own frame (x right, y up,
+// z forward): StereoCubeCamera turns faces 1..3 about `up` by 90, 180 and -90 degrees and faces
+// 4 / 5 about `right` by -90 / 90 degrees and then about `up` by 180. These are the rotations the
+// adjacency table of yrt_cube_tap.h follows.
+static const int kCubeRotation[6][3][3] = {
+    {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}},   {{0, 0, 1}, {0, 1, 0}, {-1, 0, 0}},  {{-1, 0, 0}, {0, 1, 0}, {0, 0, -1}},
+    {{0, 0, -1}, {0, 1, 0}, {1, 0, 0}},  {{-1, 0, 0}, {0, 0, 1}, {0, 1, 0}},  {{-1, 0, 0}, {0, 0, -1}, {0, -1, 0}},
+};
+
+// Do the six pixel2world frames of a stereo camera tile the sphere as the ideal cube does? Face
+// 0's frame must be a 90-degree square frustum (dir = px vx + (1 - py) vy + vz: vx, vy and
+// 2 vz + vx + vy orthogonal and of one length) and face f's linear part that frame turned by
+// kCubeRotation[f], to 1e-4 of the frame's length per entry (about 100 times the float rounding of
+// the reference's construction, far below a pixel at any supported size). A lookAt that is not
+// perpendicular to `up` fails: the reference then turns the faces about axes that are not the
+// frame's own. Empty: yes; otherwise what is wrong.
+std::string cube_cameras_defect(const GpuCamera& cam) {
+  const float* p0 = cam.p2w[0];
+  double Bm[3][3];  // columns X, Y, Z as Bm[row][col]
+  for (int r = 0; r < 3; ++r) {
+    Bm[r][0] = p0[r];
+    Bm[r][1] = p0[3 + r];
+    Bm[r][2] = 2.0 * p0[6 + r] + p0[r] + p0[3 + r];
+  }
+  double len[3], dots[3];
+  for (int c = 0; c < 3; ++c) len[c] = std::sqrt(Bm[0][c] * Bm[0][c] + Bm[1][c] * Bm[1][c] + Bm[2][c] * Bm[2][c]);
+  const double s = len[0];
+  if (!(s > 0.0) || !std::isfinite(s)) return "face 0's pixel2world frame is degenerate";
+  const double tol = 1e-4;
+  const int pairs[3][2] = {{0, 1}, {0, 2}, {1, 2}};
+  for (int k = 0; k < 3; ++k) {
+    const int a = pairs[k][0], b = pairs[k][1];
+    dots[k] = (Bm[0][a] * Bm[0][b] + Bm[1][a] * Bm[1][b] + Bm[2][a] * Bm[2][b]) / (s * s);
+  }
+  if (std::fabs(len[1] / s - 1) > tol || std::fabs(len[2] / s - 1) > tol || std::fabs(dots[0]) > tol ||
+      std::fabs(dots[1]) > tol || std::fabs(dots[2]) > tol)
+    return "face 0 is not a square 90-degree view (its pixel2world axes are not orthogonal and of one length)";
+  // C: (px, 1 - py, 1) -> the direction's coordinates in (X, Y, Z)
+  const double Cm[3][3] = {{1, 0, -0.5}, {0, 1, -0.5}, {0, 0, 0.5}};
+  for (int f = 1; f < 6; ++f) {
+    double MC[3][3], want[3][3];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        MC[r][c] = 0;
+        for (int k = 0; k < 3; ++k) MC[r][c] += kCubeRotation[f][r][k] * Cm[k][c];
+      }
+    double worst = 0;
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        want[r][c] = 0;
+        for (int k = 0; k < 3; ++k) want[r][c] += Bm[r][k] * MC[k][c];
+        worst = std::max(worst, std::fabs(cam.p2w[f][3 * c + r] - want[r][c]) / s);
+      }
+    if (!(worst <= tol)) {
+      char buf[256];
+      snprintf(buf, sizeof(buf),
+               "the cameras do not form a cube: face %d is not face 0 turned by the cube's rotation (deviation %.3g of "
+               "the frame, tolerance 1e-4); lookAt - origin must be perpendicular to up",
+               f, worst);
+      return buf;
+    }
+  }
+  return "";
+}
+
+// yrtDenoiseCube: Device::denoise over `faces` (6 or 12) square W x W frames in one launch per
+// stage. C[k], F[k]: the camera and framebuffer of slot k = eye * 6 + cubeFaceIndex % 6 (the
+// caller has validated and ordered them). The guide and filter frames are [slot][W][W] arrays;
+// each frame is filtered where it lives (filter_frame): the frames that live on the host share one
+// upload buffer and are copied back after the last iteration.
+void Device::denoiseCube(const std::vector<CameraObj*>& C, SceneObj& S, const std::vector<FrameBufferObj*>& F,
+                         const YRTDenoiseParams& p) {
+  const char* what = "yrtDenoiseCube";
+  if (!S.gpu) throw std::runtime_error(std::string(what) + ": scene not committed");
+  if (S.gpu->device != hipDevice) throw std::runtime_error(std::string(what) + ": scene committed on another HIP device");
+  if (p.iterations == 0) return;
+  const int faces = (int)C.size(), W = F[0]->width;
+  // one thread per pixel in 64-lane blocks: the grid stays far inside 2^31 blocks
+  if ((long long)faces * W * W > (1ll << 30)) throw std::runtime_error(std::string(what) + ": more than 2^30 pixels");
+  const bool demod = p.demodulate != 0;
+  HIP_CHECK(hipSetDevice(hipDevice));
+  GpuCtx& g = *ctx[0];
+  const size_t frameBytes = (size_t)faces * W * W * sizeof(float4);
+  std::vector<GpuCamera> cams(faces);
+  for (int k = 0; k < faces; ++k) cams[k] = C[k]->cam;
+  g.dCubeCams.alloc(cams.size() * sizeof(GpuCamera));
+  g.dGuidePos.alloc(frameBytes);
+  g.dGuideNrm.alloc(frameBytes);
+  if (demod) g.dGuideAlbedo.alloc(frameBytes);
+  HIP_CHECK(hipMemcpyAsync(g.dCubeCams.p, cams.data(), cams.size() * sizeof(GpuCamera), hipMemcpyHostToDevice, stream));
+  evGuides.time(kernelTiming, stream, [&] {
+    launch_guides_cube(S.gpu->view, g.dCubeCams.as<GpuCamera>(), faces, W, g.dGuidePos.as<float4>(),
+                       g.dGuideNrm.as<float4>(), demod ? g.dGuideAlbedo.as<float4>() : nullptr, stream);
+  });
+  HIP_CHECK(hipGetLastError());
+
+  // the frames: in the block, or uploaded side by side (16-byte aligned) into dFilterFb
+  const size_t fbBytes = F[0]->stride * (size_t)W, fbSlot = (fbBytes + 15) / 16 * 16;
+  std::vector<FrameIO> ios(faces);
+  std::vector<int> ids(faces);
+  std::vector<char> onHost(faces, 0);
+  size_t uploads = 0;
+  for (int k = 0; k < faces; ++k) {
+    ids[k] = F[k]->cur;
+    const FilterFrame ff = filter_frame(*F[k], ids[k]);
+    ios[k] = ff.io;
+    if (!ff.inBlock) {
+      onHost[k] = 1;
+      ++uploads;
+    }
+  }
+  HIP_CHECK(hipSetDevice(hipDevice));  // a read-back may have selected the frame's device
+  if (uploads) {
+    g.dFilterFb.alloc(uploads * fbSlot);
+    size_t u = 0;
+    for (int k = 0; k < faces; ++k) {
+      if (!onHost[k]) continue;
+      ios[k].pixels = (char*)g.dFilterFb.p + u++ * fbSlot;
+      HIP_CHECK(hipMemcpyAsync(ios[k].pixels, F[k]->buffer(ids[k]), fbBytes, hipMemcpyHostToDevice, stream));
+    }
+  }
+  g.dCubeIo.alloc(ios.size() * sizeof(FrameIO));
+  HIP_CHECK(hipMemcpyAsync(g.dCubeIo.p, ios.data(), ios.size() * sizeof(FrameIO), hipMemcpyHostToDevice, stream));
+  g.dFilter[0].alloc(frameBytes);
+  if (p.iterations > 1) g.dFilter[1].alloc(frameBytes);
+  Demodulation dm;
+  if (demod) {
+    g.dFilterMod.alloc(frameBytes);
+    dm.albedo4 = g.dGuideAlbedo.as<float4>();
+    dm.mod4 = g.dFilterMod.as<float4>();
+    dm.albedoFloor = p.albedoFloor;
+    dm.albedoPower = p.albedoPower;
+  }
+  evFilter.time(kernelTiming, stream, [&] {
+    launch_atrous_load_cube(g.dCubeIo.as<FrameIO>(), faces, W, g.dFilter[0].as<float4>(), dm, stream);
+    AtrousParams ap;
+    memset(&ap, 0, sizeof(ap));
+    ap.width = W;
+    ap.height = W;
+    ap.sigmaNormal = p.sigmaNormal;
+    ap.sigmaPosition = p.sigmaPosition;
+    for (int i = 0; i < p.iterations; ++i) {
+      const bool last = i + 1 == p.iterations;
+      ap.step = 1 << i;
+      const float sc = p.sigmaColor > 0.f ? p.sigmaColor / (float)(1 << i) : 0.f;  // as Device::denoise
+      ap.rcpSigmaColor2 = sc > 0.f ? 1.0f / (sc * sc) : 0.f;
+      launch_atrous_cube(ap, faces, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(), g.dFilter[i & 1].as<float4>(),
+                         last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(), last ? g.dCubeIo.as<FrameIO>() : nullptr,
+                         dm.mod4, stream);
+    }
+  });
+  HIP_CHECK(hipGetLastError());
+  for (int k = 0; k < faces; ++k)
+    if (onHost[k])
+      HIP_CHECK(hipMemcpyAsync(F[k]->buffer(ids[k]), ios[k].pixels, fbBytes, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream));
   evGuides.read(msGuides);
   evFilter.read(msFilter);

@@ -3,7 +3,7 @@
 //   device.cpp         Device's ray queries, frame read-back, scene commit
 //   render.cpp         Device::render (the frame job), Device::render_shard (one device's share)
 //   render_job.{h,cpp} the batch plan and the wavefront lane scheduler render_shard runs
-//   denoise.cpp        Device::guides, Device::denoise
+//   denoise.cpp        Device::guides, Device::denoise, Device::denoiseCube and its cube check
 //   gather_device.cpp  Device::gather_local, Device::gather_process
 //   api_objects.cpp, api_tools.cpp  the extern "C" entry points (include/yrt_device.h)
 #pragma once
@@ -94,6 +94,8 @@ struct GpuCtx {
   // denoise (yrtRenderGuides / yrtDenoiseFrameBuffer): the guide frames, the filter's two
   // ping-pong float4 frames and the upload of a frame that lives in host pixels
   DevBuf dGuidePos, dGuideNrm, dGuideAlbedo, dFilter[2], dFilterMod, dFilterFb;
+  // yrtDenoiseCube: the faces' camera records and their FrameIO records
+  DevBuf dCubeCams, dCubeIo;
   // The frames a job renders into (float RGB and RGB8 rows, frame-major). On the primary
   // device a job's framebuffers keep a reference to their block until rtMapFrameBuffer reads
   // them back, so the next job renders into the spare (or a fresh) block meanwhile.
@@ -370,7 +372,20 @@ class Device {
   EvPair evGuides, evFilter;
   float msGuides = 0.f, msFilter = 0.f;
   void denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDenoiseParams& p);
+  // where buffer `id` of F lives for the filter: in this device's frame block, or on the host
+  struct FilterFrame {
+    FrameIO io;
+    bool inBlock;
+  };
+  FilterFrame filter_frame(FrameBufferObj& F, int id);
+  // yrtDenoiseCube over validated slots k = eye * 6 + face: C[k] through F[k]
+  void denoiseCube(const std::vector<CameraObj*>& C, SceneObj& S, const std::vector<FrameBufferObj*>& F,
+                   const YRTDenoiseParams& p);
 };
+
+// yrtDenoiseCube's host check: empty when the six faces of a committed stereo camera are the ideal
+// cube's (denoise.cpp), otherwise what is wrong
+std::string cube_cameras_defect(const GpuCamera& cam);
 
 }  // namespace yrt
 

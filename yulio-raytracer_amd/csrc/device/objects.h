@@ -168,7 +168,7 @@ struct SceneObj : Object {
 
 // ---------------------------------------------------------------- camera / renderer / fb
 struct CameraObj : Object {
-  GpuCamera cam;
+  GpuCamera cam{};  // type 0 until the first commit
   explicit CameraObj(const std::string& t) : Object(Kind::CAMERA, t) {}
   void commit() override;
 };

@@ -318,6 +318,10 @@ void RtState::parseCommandLine(const std::vector<std::string>& tokens, const std
       const int v = cin.getInt();
       if (v != 0 && v != 1) throw std::runtime_error("-denoise-albedo: 0 or 1 expected");
       denoiseAlbedo = v == 1;
+    } else if (tag == "-denoise-cube") {
+      const int v = cin.getInt();
+      if (v != 0 && v != 1) throw std::runtime_error("-denoise-cube: 0 or 1 expected");
+      denoiseCube = v == 1;
     } else if (tag == "-depth") {
       depth = cin.getInt();
       check(dev, yrtSetInt1(dev, renderer, "maxDepth", depth), "rtSetInt1");
@@ -597,8 +601,7 @@ void RtState::renderFprFace(size_t i) {
   for (int j = 0; j < numBuffers; ++j) check(dev, yrtSwapBuffers(dev, frameBuffer), "rtSwapBuffers");
 }
 
-void RtState::denoiseFrame(YRTHandle cam, YRTHandle sc, YRTHandle fb) {
-  if (denoise <= 0) return;
+YRTDenoiseParams RtState::denoiseParams() const {
   YRTDenoiseParams p;
   p.size = (uint32_t)(offsetof(YRTDenoiseParams, iterations) + sizeof(p.iterations));  // the weights: defaults
   if (denoiseAlbedo) {
@@ -609,6 +612,12 @@ void RtState::denoiseFrame(YRTHandle cam, YRTHandle sc, YRTHandle fb) {
     p.albedoPower = (float)rcpGamma;
   }
   p.iterations = denoise;
+  return p;
+}
+
+void RtState::denoiseFrame(YRTHandle cam, YRTHandle sc, YRTHandle fb) {
+  if (denoise <= 0) return;
+  const YRTDenoiseParams p = denoiseParams();
   check(dev, yrtDenoiseFrameBuffer(dev, cam, sc, fb, &p), "yrtDenoiseFrameBuffer");
 }
 
@@ -626,6 +635,12 @@ void RtState::renderCube(const std::vector<YRTHandle>& cams) {
   YRTHandle sc = createScene();
   check(dev, yrtRenderFrames(dev, renderer, cams.data(), (int)cams.size(), sc, tonemapper, cubeFrameBuffers.data(), 0),
         "rtRenderFrames");
+  if (denoise > 0 && denoiseCube) {
+    // -denoise-cube 1: the job's faces as one surface, taps crossing the cube's edges
+    const YRTDenoiseParams p = denoiseParams();
+    check(dev, yrtDenoiseCube(dev, cams.data(), (int)cams.size(), sc, cubeFrameBuffers.data(), &p), "yrtDenoiseCube");
+    return;
+  }
   for (size_t k = 0; k < cams.size(); ++k) denoiseFrame(cams[k], sc, cubeFrameBuffers[k]);
 }
 

@@ -4,6 +4,7 @@
 
 #include "yrt_kernels.h"
 #include "yrt_wave.h"
+#include "../common/yrt_cube_tap.h"
 #include "../common/yrt_libm.h"
 
 namespace yrt {
@@ -18,13 +19,20 @@ __device__ __forceinline__ size_t fb_channel(const FrameIO& io, int x, int y) {
 // DEMOD (YRTDenoiseParams::demodulate): a hit pixel's modulation m = max(albedo, floor) ^ power
 // per channel goes to mod4 and the filter's input is d_0 = c_0 / m (IEEE divisions); a miss
 // pixel, which the filter neither reads nor writes, keeps c_0 and gets m = 1.
-template <bool DEMOD>
+// CUBE (yrtDenoiseCube): dst, albedo4 and mod4 are [face][W][W] arrays, blockIdx.y is the face
+// and face f's pixels are those of faceIo[f] (frames of io's size).
+template <bool DEMOD, bool CUBE = false>
 __global__ __launch_bounds__(YRT_BLOCK) void k_atrous_load(FrameIO io, float4* __restrict__ dst,
                                                            const float4* __restrict__ albedo4, float albedoFloor,
-                                                           float albedoPower, float4* __restrict__ mod4) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+                                                           float albedoPower, float4* __restrict__ mod4,
+                                                           const FrameIO* __restrict__ faceIo) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)io.width * io.height) return;
   const int y = (int)(i / io.width), x = (int)(i - (long long)y * io.width);
+  if constexpr (CUBE) {
+    i += (long long)blockIdx.y * io.width * io.height;
+    io = faceIo[blockIdx.y];
+  }
   const size_t o = fb_channel(io, x, y);
   float4 c;
   if (io.bytes) {
@@ -58,21 +66,28 @@ __device__ __forceinline__ float atrous_h(int d) { return d == 0 ? 0.375f : (d =
 //   w_c = exp(-|c_p - c_q|^2 / sigmaColor_i^2)                  (rcpSigmaColor2 = 0: off)
 // Taps outside the image or on a miss are skipped; the centre tap weighs h(0)^2 exactly. The
 // mean is taken as c_p + sum w (c_q - c_p) / sum w, so a constant frame stays what it is.
-// A miss pixel is not written. The last iteration (out != null) stores into the framebuffer:
+// A miss pixel is not written. The last iteration (out, or CUBE's faceOut, != null) stores into the framebuffer:
 // floats as they are, bytes as k_resolve_pixels quantizes them; alpha and row padding are
 // not touched. DEMOD: the frames hold the demodulated signal d (k_atrous_load), every weight
 // acts on d, and the last iteration stores d_n m with the modulation of mod4.
-template <bool DEMOD>
+// CUBE (yrtDenoiseCube): the frames are [face][W][W] arrays, six faces per eye in cubeFaceIndex
+// order, and blockIdx.y is the face; a tap that leaves its face reads the pixel yrt_cube_tap
+// names on a neighbour of the same eye (a corner tap is skipped), with the same weights; the last
+// iteration stores face f's pixels into faceOut[f].
+template <bool DEMOD, bool CUBE = false>
 __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const float4* __restrict__ pos4,
                                                       const float4* __restrict__ nrm4, const float4* __restrict__ src,
                                                       float4* __restrict__ dst, FrameIO out,
-                                                      const float4* __restrict__ mod4) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+                                                      const float4* __restrict__ mod4,
+                                                      const FrameIO* __restrict__ faceOut) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)ap.width * ap.height) return;
+  const int y = (int)(i / ap.width), x = (int)(i - (long long)y * ap.width);
+  const int face = CUBE ? (int)blockIdx.y : 0;
+  if constexpr (CUBE) i += (long long)face * ap.width * ap.height;
   const float INF = __int_as_float(0x7f800000);
   const float4 pp = pos4[i];
   if (!(pp.w < INF)) return;
-  const int y = (int)(i / ap.width), x = (int)(i - (long long)y * ap.width);
   const float4 n4 = nrm4[i], c4 = src[i];
   const V3 xp = v3(pp.x, pp.y, pp.z), np = v3(n4.x, n4.y, n4.z), cp = v3(c4.x, c4.y, c4.z);
   const float rcpPlane = 1.0f / (ap.sigmaPosition * pp.w);
@@ -80,11 +95,19 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const flo
   float wsum = atrous_h(0) * atrous_h(0);
   for (int dy = -2; dy <= 2; ++dy) {
     const long long qy = (long long)y + (long long)dy * ap.step;
-    if (qy < 0 || qy >= ap.height) continue;
+    if (!CUBE && (qy < 0 || qy >= ap.height)) continue;
     for (int dx = -2; dx <= 2; ++dx) {
       const long long qx = (long long)x + (long long)dx * ap.step;
-      if (qx < 0 || qx >= ap.width || (dx == 0 && dy == 0)) continue;
-      const size_t j = (size_t)qy * ap.width + (size_t)qx;
+      size_t j;
+      if constexpr (CUBE) {
+        if (dx == 0 && dy == 0) continue;
+        int g, tx, ty;  // the host keeps W and the step inside yrt_cube_tap's range
+        if (yrt_cube_tap(ap.width, face % 6, (int)qx, (int)qy, &g, &tx, &ty) != 1) continue;
+        j = ((size_t)(face - face % 6 + g) * ap.height + (size_t)ty) * ap.width + (size_t)tx;
+      } else {
+        if (qx < 0 || qx >= ap.width || (dx == 0 && dy == 0)) continue;
+        j = (size_t)qy * ap.width + (size_t)qx;
+      }
       const float4 pq = pos4[j];
       if (!(pq.w < INF)) continue;
       const float4 nq = nrm4[j], cq4 = src[j];
@@ -98,7 +121,7 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const flo
     }
   }
   V3 c = cp + sum * (1.0f / wsum);
-  if (!out.pixels) {
+  if (CUBE ? !faceOut : !out.pixels) {
     dst[i] = make_float4(c.x, c.y, c.z, 0.f);
     return;
   }
@@ -106,6 +129,7 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const flo
     const float4 m = mod4[i];
     c = c * v3(m.x, m.y, m.z);
   }
+  if constexpr (CUBE) out = faceOut[face];
   const size_t o = fb_channel(out, x, y);
   if (out.bytes) {
     uint8_t* p = (uint8_t*)out.pixels + o;

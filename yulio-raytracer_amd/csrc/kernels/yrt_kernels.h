@@ -260,6 +260,18 @@ void launch_atrous_load(const FrameIO& io, float4* dst, const Demodulation& dm, 
 // times the modulation mod4 when that is not null)
 void launch_atrous(const AtrousParams& ap, const float4* pos4, const float4* nrm4, const float4* src, float4* dst,
                    const FrameIO& out, const float4* mod4, hipStream_t s);
+// The cube forms (yrtDenoiseCube): one launch over `faces` (6 or 12) square width x width frames,
+// six per eye in cubeFaceIndex order, the float4 frames being [face][width][width] arrays. cams
+// and faceIo are device arrays of one record per face; face f's guides are launch_guides' for
+// cams[f] and its pixels those of faceIo[f]. launch_atrous_cube: a tap that leaves its face reads
+// the neighbouring face of the same eye (common/yrt_cube_tap.h); faceOut != null: the last
+// iteration, stored into the faces' framebuffers.
+void launch_guides_cube(const SceneView& sv, const GpuCamera* cams, int faces, int width, float4* pos4, float4* nrm4,
+                        float4* albedo4, hipStream_t s);
+void launch_atrous_load_cube(const FrameIO* faceIo, int faces, int width, float4* dst, const Demodulation& dm,
+                             hipStream_t s);
+void launch_atrous_cube(const AtrousParams& ap, int faces, const float4* pos4, const float4* nrm4, const float4* src,
+                        float4* dst, const FrameIO* faceOut, const float4* mod4, hipStream_t s);
 // BVH refit after faceCamera updates: rewrite triangles [firstTri, firstTri+numTris) (global
 // ids) from the vertex buffer in every leaf slot that references them (leafSlots[leafStart[g]
 // .. leafStart[g+1])), then refit one tree level of nodes (call deepest level first)

@@ -371,13 +371,10 @@ class Device:
             d.update(demodulate=p.demodulate, albedo_power=p.albedoPower, albedo_floor=p.albedoFloor)
         return d
 
-    def denoise(self, camera, scene, frameBuffer, iterations=None, sigma_color=None, sigma_normal=None,
-                sigma_position=None, demodulate=None, albedo_power=None, albedo_floor=None):
-        """Filters frameBuffer's current frame in place, guided by the first hits seen through
-        `camera` (yrtDenoiseFrameBuffer). None: the library's default (5 iterations, sigma_color 1,
-        sigma_normal 64, sigma_position 0.02); sigma_color <= 0 turns the colour weight off.
-        demodulate: filter frame / m and store the result x m, m = max(albedo, albedo_floor) ^
-        albedo_power; albedo_power is 1 / gamma of the frame's tone mapper (defaults 0, 1, 1/255)."""
+    @staticmethod
+    def _denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_position=None, demodulate=None,
+                        albedo_power=None, albedo_floor=None):
+        """The library's defaults overlaid by the keywords that are not None."""
         p = N.DenoiseParams(size=C.sizeof(N.DenoiseParams))
         if N.dev.yrtDenoiseDefaults(C.byref(p)) != 0:
             raise RuntimeError("yrtDenoiseDefaults failed")
@@ -395,7 +392,31 @@ class Device:
             p.albedoPower = float(albedo_power)
         if albedo_floor is not None:
             p.albedoFloor = float(albedo_floor)
+        return p
+
+    def denoise(self, camera, scene, frameBuffer, iterations=None, sigma_color=None, sigma_normal=None,
+                sigma_position=None, demodulate=None, albedo_power=None, albedo_floor=None):
+        """Filters frameBuffer's current frame in place, guided by the first hits seen through
+        `camera` (yrtDenoiseFrameBuffer). None: the library's default (5 iterations, sigma_color 1,
+        sigma_normal 64, sigma_position 0.02); sigma_color <= 0 turns the colour weight off.
+        demodulate: filter frame / m and store the result x m, m = max(albedo, albedo_floor) ^
+        albedo_power; albedo_power is 1 / gamma of the frame's tone mapper (defaults 0, 1, 1/255)."""
+        p = self._denoise_params(iterations, sigma_color, sigma_normal, sigma_position, demodulate, albedo_power,
+                                 albedo_floor)
         self._rc(N.dev.yrtDenoiseFrameBuffer(self.h, camera, scene, frameBuffer, C.byref(p)), "denoise")
+
+    def denoise_cube(self, cameras, scene, frameBuffers, **kw):
+        """The same filter over the 6 (one eye) or 12 faces of a stereo cube as one surface: taps
+        cross the cube's edges onto the neighbouring face of the same eye (yrtDenoiseCube).
+        frameBuffers[k] holds the frame rendered through the "stereo" camera cameras[k]; keywords
+        as denoise."""
+        n = len(cameras)
+        if len(frameBuffers) != n:
+            raise ValueError("one framebuffer per camera")
+        p = self._denoise_params(**kw)
+        cams = (C.c_void_p * n)(*cameras)
+        fbs = (C.c_void_p * n)(*frameBuffers)
+        self._rc(N.dev.yrtDenoiseCube(self.h, cams, n, scene, fbs, C.byref(p)), "denoise_cube")
 
     def denoise_times(self):
         """(ms of the last guide pass, ms of the last filter) by HIP events; set_kernel_timing first."""
@@ -615,6 +636,17 @@ class ShardHub:
         if r < 0:
             raise RuntimeError(N.dev.yrtShardHubLastError().decode())
         return out[:(self.world - 1) * recv_bytes_per_rank] if out is not None else None
+
+
+def cube_tap(W, face, qx, qy):
+    """Where the filter tap (qx, qy) of cube face `face` (0..5 within its eye, W x W pixels) lands:
+    (g, x, y), the face and pixel, or None for a corner tap, which the cube denoise skips
+    (yrtDebugCubeTap)."""
+    g, x, y = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = N.dev.yrtDebugCubeTap(int(W), int(face), int(qx), int(qy), C.byref(g), C.byref(x), C.byref(y))
+    if rc < 0:
+        raise ValueError("cube_tap: arguments out of range")
+    return (g.value, x.value, y.value) if rc == 1 else None
 
 
 def sample_table(spp, sets, iteration, num1D, num2D, filter="bspline"):

@@ -221,6 +221,11 @@ try:  # the denoise stage; absent from older builds selected with YRT_LIB_DIR
     _sig(dev, "yrtRenderAlbedo", i32, vp, vp, vp, i32, i32, vp)
 except AttributeError:
     pass
+try:  # the cube denoise; absent from older builds selected with YRT_LIB_DIR
+    _sig(dev, "yrtDenoiseCube", i32, vp, C.POINTER(vp), i32, vp, C.POINTER(vp), C.POINTER(DenoiseParams))
+    _sig(dev, "yrtDebugCubeTap", i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32))
+except AttributeError:
+    pass
 _sig(dev, "yrtDebugDecodeImage", i32, cstr, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, sz)
 _sig(dev, "yrtDebugSampleTable", i32, i32, i32, i32, i32, i32, cstr, PF, sz)
 
