@@ -13,6 +13,7 @@ import yrt
 from yrt import _native as N
 
 import denoise_ref as ref
+from denoise_albedo_ref import mapped, pixels, reldev
 from helpers import c1_args
 from trace_scenes import MeshScene
 
@@ -27,37 +28,6 @@ DEFAULTS = dict(sigma_color=1.0, sigma_normal=64.0, sigma_position=float(np.floa
 # 1e-4 ceiling (float32 epsilon x 25 taps x 5 iterations x the exponent 64 of the normal weight).
 FILTER_MEASURED = 1.17e-6
 FILTER_BOUND = min(8 * FILTER_MEASURED, 1e-4)
-
-
-# ----------------------------------------------------------------------------- helpers
-def _stride(fmt, w):
-    return {"RGB8": (3 * w + 3) // 4 * 4, "RGBA8": 4 * w, "RGB_FLOAT32": 12 * w, "RGBA_FLOAT32": 16 * w}[fmt]
-
-
-def _mapped(d, fb, fmt, w, h, write=None):
-    """The mapped framebuffer's bytes, row padding included, as (h, stride) uint8 (a copy); write:
-    bytes of the same shape stored into the mapped pixels first."""
-    p = d.rtMapFrameBuffer(fb)
-    a = np.ctypeslib.as_array((C.c_uint8 * (_stride(fmt, w) * h)).from_address(p)).reshape(h, _stride(fmt, w))
-    if write is not None:
-        a[...] = write
-    a = a.copy()
-    d.rtUnmapFrameBuffer(fb)
-    return a
-
-
-def _pixels(raw, fmt, w):
-    """(h, w, channels) view of _mapped bytes: uint8 or float32."""
-    h = raw.shape[0]
-    if fmt == "RGB8":
-        return raw[:, :3 * w].reshape(h, w, 3)
-    if fmt == "RGBA8":
-        return raw.reshape(h, w, 4)
-    return raw.view(np.float32).reshape(h, w, 3 if fmt == "RGB_FLOAT32" else 4)
-
-
-def _reldev(got, want):
-    return float((np.abs(got.astype(np.float64) - want) / np.maximum(np.abs(want), 1 / 255)).max())
 
 
 class Quads:
@@ -84,7 +54,7 @@ class Quads:
 
     def raw(self, fmt, w=W, h=H):
         if (fmt, w, h) not in self._raw:
-            self._raw[fmt, w, h] = _mapped(self.dev, self.render(fmt, w, h), fmt, w, h)
+            self._raw[fmt, w, h] = mapped(self.dev, self.render(fmt, w, h), fmt, w, h)
         return self._raw[fmt, w, h]
 
     def guides(self, w=W, h=H):
@@ -95,11 +65,11 @@ class Quads:
     def denoised(self, fmt, w=W, h=H, **kw):
         fb = self.render(fmt, w, h)
         self.dev.denoise(self.ms.camera, self.ms.scene, fb, **kw)
-        return _mapped(self.dev, fb, fmt, w, h)
+        return mapped(self.dev, fb, fmt, w, h)
 
     def expect(self, fmt, w=W, h=H, iterations=5):
         """The numpy filter on the GPU's own undenoised frame and guides: (h, w, 3) float64."""
-        px = _pixels(self.raw(fmt, w, h), fmt, w)[..., :3]
+        px = pixels(self.raw(fmt, w, h), fmt, w)[..., :3]
         c0 = px.astype(np.float64) / 255.0 if px.dtype == np.uint8 else px.astype(np.float64)
         pos, nrm = self.guides(w, h)
         return ref.atrous(c0, pos, nrm, iterations, **DEFAULTS)
@@ -280,12 +250,12 @@ def test_guide_normals_interpolate(gpu_device):
 def test_filter_matches_numpy(quads, fmt, iterations):
     """Measured on an MI355X: 4.5e-7, 8.7e-7, 8.6e-7 for 1, 3, 5 iterations (FILTER_MEASURED). Step
     16 of the fifth iteration sends taps outside the 40 x 24 frame on every side."""
-    raw = _pixels(quads.raw(fmt), fmt, W)
+    raw = pixels(quads.raw(fmt), fmt, W)
     assert (raw[..., :3].max(-1) > 0.01).mean() > 0.2, "the scene must be lit"
-    got = _pixels(quads.denoised(fmt, iterations=iterations), fmt, W)
+    got = pixels(quads.denoised(fmt, iterations=iterations), fmt, W)
     want = quads.expect(fmt, iterations=iterations)
     hit = np.isfinite(quads.guides()[0][..., 3])
-    dev = _reldev(got[..., :3][hit], want[hit])
+    dev = reldev(got[..., :3][hit], want[hit])
     print(f"filter {fmt} x{iterations}: relative deviation {dev:.3g}")
     assert np.abs(got[..., :3][hit].astype(np.float64) - raw[..., :3][hit]).max() > 1e-3, "the filter must act"
     assert dev <= FILTER_BOUND
@@ -301,15 +271,15 @@ def test_filter_8bit(quads, fmt):
     RGB8 rows (width 38: 114 of 116 bytes) and the miss pixels are untouched."""
     d = quads.dev
     fb = quads.render(fmt, W8, H)
-    raw = _mapped(d, fb, fmt, W8, H)
+    raw = mapped(d, fb, fmt, W8, H)
     if fmt == "RGB8":  # mark the padding, so that a store into it shows
         raw[:, 3 * W8:] = 0xA5
-        _mapped(d, fb, fmt, W8, H, write=raw)
-    assert np.array_equal(raw, _mapped(d, fb, fmt, W8, H))
+        mapped(d, fb, fmt, W8, H, write=raw)
+    assert np.array_equal(raw, mapped(d, fb, fmt, W8, H))
     d.denoise(quads.ms.camera, quads.ms.scene, fb)
-    out = _mapped(d, fb, fmt, W8, H)
-    got, before = _pixels(out, fmt, W8), _pixels(raw, fmt, W8)
-    assert np.array_equal(_pixels(quads.raw(fmt, W8, H), fmt, W8), before)
+    out = mapped(d, fb, fmt, W8, H)
+    got, before = pixels(out, fmt, W8), pixels(raw, fmt, W8)
+    assert np.array_equal(pixels(quads.raw(fmt, W8, H), fmt, W8), before)
     want = ref.quantize(quads.expect(fmt, W8, H))
     hit = np.isfinite(quads.guides(W8, H)[0][..., 3])
     diff = np.abs(got[..., :3][hit].astype(int) - want[hit].astype(int))
@@ -322,7 +292,7 @@ def test_filter_8bit(quads, fmt):
     else:
         assert np.all(out[:, 3 * W8:] == 0xA5)
     # the frame filtered where it was rendered (RGB8: in HBM) holds the same pixels
-    assert np.array_equal(_pixels(quads.denoised(fmt, W8, H), fmt, W8), got)
+    assert np.array_equal(pixels(quads.denoised(fmt, W8, H), fmt, W8), got)
 
 
 @pytest.mark.gpu
@@ -330,11 +300,11 @@ def test_filter_8bit(quads, fmt):
 def test_zero_iterations_write_nothing(quads, fmt):
     w = W8 if fmt == "RGB8" else W
     fb = quads.render(fmt, w, H)
-    raw = _mapped(quads.dev, fb, fmt, w, H)
+    raw = mapped(quads.dev, fb, fmt, w, H)
     quads.dev.denoise(quads.ms.camera, quads.ms.scene, fb, iterations=0)
-    assert np.array_equal(_mapped(quads.dev, fb, fmt, w, H), raw)
+    assert np.array_equal(mapped(quads.dev, fb, fmt, w, H), raw)
     # and on a frame not mapped yet (the RGB8 padding of a frame in HBM is whatever the block held)
-    assert np.array_equal(_pixels(quads.denoised(fmt, w, H, iterations=0), fmt, w), _pixels(raw, fmt, w))
+    assert np.array_equal(pixels(quads.denoised(fmt, w, H, iterations=0), fmt, w), pixels(raw, fmt, w))
 
 
 @pytest.mark.gpu
@@ -346,12 +316,12 @@ def test_constant_frame_is_kept(quads, fmt):
     fb = quads.render(fmt)
     hit = np.isfinite(quads.guides()[0][..., 3])
     value = np.float32([0.7231, 0.05, 3.5])
-    px = _pixels(_mapped(d, fb, fmt, W, H), fmt, W).copy()
+    px = pixels(mapped(d, fb, fmt, W, H), fmt, W).copy()
     px[..., :3] = np.float32(9.0)
     px[hit, :3] = value
-    _mapped(d, fb, fmt, W, H, write=px.view(np.uint8).reshape(H, -1))
+    mapped(d, fb, fmt, W, H, write=px.view(np.uint8).reshape(H, -1))
     d.denoise(quads.ms.camera, quads.ms.scene, fb)
-    out = _pixels(_mapped(d, fb, fmt, W, H), fmt, W)
+    out = pixels(mapped(d, fb, fmt, W, H), fmt, W)
     assert np.all(np.abs(out[hit][:, :3] - value) <= 2 * np.spacing(value))
     assert np.array_equal(out[~hit], px[~hit])
 
@@ -363,11 +333,11 @@ def test_frame_is_filtered_where_it_lives(quads, fmt):
     the second map returns the filtered frame."""
     w = W8 if fmt == "RGB8" else W
     d = quads.dev
-    first = _pixels(quads.denoised(fmt, w, H), fmt, w)
+    first = pixels(quads.denoised(fmt, w, H), fmt, w)
     fb = quads.render(fmt, w, H)
-    raw = _pixels(_mapped(d, fb, fmt, w, H), fmt, w)
+    raw = pixels(mapped(d, fb, fmt, w, H), fmt, w)
     d.denoise(quads.ms.camera, quads.ms.scene, fb)
-    second = _pixels(_mapped(d, fb, fmt, w, H), fmt, w)
+    second = pixels(mapped(d, fb, fmt, w, H), fmt, w)
     assert not np.array_equal(second, raw)
     assert np.array_equal(first.view(np.uint8), second.view(np.uint8))
 
@@ -401,7 +371,7 @@ def test_cube_job_faces(quads):
         hit = np.isfinite(pos[..., 3])
         assert 50 < hit.sum() < S * S
         want = ref.atrous(raw, pos, nrm, 3, **DEFAULTS)
-        dev = _reldev(got[hit], want[hit])
+        dev = reldev(got[hit], want[hit])
         print(f"cube face: relative deviation {dev:.3g}")
         assert dev <= FILTER_BOUND
         assert np.array_equal(got[~hit], raw[~hit]) and not np.array_equal(got[hit], raw[hit])

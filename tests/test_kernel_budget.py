@@ -38,6 +38,19 @@ def test_trace_kernels_fit_their_waves(res):
     assert any("k_trace<false, false, 1>" in k for k in trace)
 
 
+def test_denoise_is_one_kernel_family(res):
+    """A frame and a cube share their kernels: the guide pass with and without the
+    albedo, the load plain and demodulated, the filter plain and demodulated with taps that stop at
+    the border or wrap. The filter kernels run once per pixel and iteration and hold no scratch."""
+    family = {p: {k: v for k, v in res.items() if k.startswith(f"void yrt::{p}<") or k.startswith(f"yrt::{p}<")}
+              for p in ("k_guides", "k_atrous_load", "k_atrous")}
+    assert {p: len(v) for p, v in family.items()} == {"k_guides": 2, "k_atrous_load": 2, "k_atrous": 4}, \
+        {p: sorted(v) for p, v in family.items()}
+    for p in ("k_atrous_load", "k_atrous"):
+        for name, r in family[p].items():
+            assert r["scratch"] == 0, (name, r)
+
+
 def test_shade_kernels_hold_four_waves(res):
     shade = {k: v for k, v in res.items() if "k_shade<" in k}
     assert shade

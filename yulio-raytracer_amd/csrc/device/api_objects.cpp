@@ -715,40 +715,37 @@ int yrtDenoiseDefaults(YRTDenoiseParams* p) {
   return 0;
 }
 
+// yrtRenderGuides / yrtRenderAlbedo: the guide pass of one width x height view, then each frame
+// of `out` (a guide buffer of ctx[0], the host frame it goes to) copied to the host
+static void render_guides(Device& D, const char* what, YRTHandle camera, YRTHandle scene, int width, int height,
+                          bool albedo, std::initializer_list<std::pair<DevBuf GpuCtx::*, float*>> out) {
+  if (!D.gpu) throw std::runtime_error(std::string(what) + ": host-only device (created with parms \"host\")");
+  auto C = D.get<CameraObj>(camera, "camera");
+  auto S = D.get<SceneObj>(scene, "scene");
+  bool null = !C || !S;
+  for (const auto& o : out) null = null || !o.second;
+  if (null) throw std::runtime_error(std::string(what) + ": null handle or pointer");
+  if (width < 1 || height < 1) throw std::runtime_error(std::string(what) + ": empty frame");
+  D.guides({C.get()}, *S, width, height, what, albedo);
+  const size_t bytes = (size_t)width * height * sizeof(float4);
+  for (const auto& o : out)
+    HIP_CHECK(hipMemcpyAsync(o.second, ((*D.ctx[0]).*o.first).p, bytes, hipMemcpyDeviceToHost, D.stream));
+  HIP_CHECK(hipStreamSynchronize(D.stream));
+  D.evGuides.read(D.msGuides);
+}
+
 int yrtRenderGuides(YRTDevice dev, YRTHandle camera, YRTHandle scene, int width, int height, float* pos4Host,
                     float* nrm4Host) {
   DEV_GUARD(dev, -1)
-  Device& D = *dev->d;
-  if (!D.gpu) throw std::runtime_error("yrtRenderGuides: host-only device (created with parms \"host\")");
-  auto C = D.get<CameraObj>(camera, "camera");
-  auto S = D.get<SceneObj>(scene, "scene");
-  if (!C || !S || !pos4Host || !nrm4Host) throw std::runtime_error("yrtRenderGuides: null handle or pointer");
-  if (width < 1 || height < 1) throw std::runtime_error("yrtRenderGuides: empty frame");
-  D.guides(*C, *S, width, height, "yrtRenderGuides");
-  GpuCtx& g = *D.ctx[0];
-  const size_t bytes = (size_t)width * height * sizeof(float4);
-  HIP_CHECK(hipMemcpyAsync(pos4Host, g.dGuidePos.p, bytes, hipMemcpyDeviceToHost, D.stream));
-  HIP_CHECK(hipMemcpyAsync(nrm4Host, g.dGuideNrm.p, bytes, hipMemcpyDeviceToHost, D.stream));
-  HIP_CHECK(hipStreamSynchronize(D.stream));
-  D.evGuides.read(D.msGuides);
+  render_guides(*dev->d, "yrtRenderGuides", camera, scene, width, height, false,
+                {{&GpuCtx::dGuidePos, pos4Host}, {&GpuCtx::dGuideNrm, nrm4Host}});
   return 0;
   DEV_END(-1)
 }
 
 int yrtRenderAlbedo(YRTDevice dev, YRTHandle camera, YRTHandle scene, int width, int height, float* albedo4Host) {
   DEV_GUARD(dev, -1)
-  Device& D = *dev->d;
-  if (!D.gpu) throw std::runtime_error("yrtRenderAlbedo: host-only device (created with parms \"host\")");
-  auto C = D.get<CameraObj>(camera, "camera");
-  auto S = D.get<SceneObj>(scene, "scene");
-  if (!C || !S || !albedo4Host) throw std::runtime_error("yrtRenderAlbedo: null handle or pointer");
-  if (width < 1 || height < 1) throw std::runtime_error("yrtRenderAlbedo: empty frame");
-  D.guides(*C, *S, width, height, "yrtRenderAlbedo", true);
-  GpuCtx& g = *D.ctx[0];
-  const size_t bytes = (size_t)width * height * sizeof(float4);
-  HIP_CHECK(hipMemcpyAsync(albedo4Host, g.dGuideAlbedo.p, bytes, hipMemcpyDeviceToHost, D.stream));
-  HIP_CHECK(hipStreamSynchronize(D.stream));
-  D.evGuides.read(D.msGuides);
+  render_guides(*dev->d, "yrtRenderAlbedo", camera, scene, width, height, true, {{&GpuCtx::dGuideAlbedo, albedo4Host}});
   return 0;
   DEV_END(-1)
 }
@@ -763,7 +760,7 @@ int yrtDenoiseFrameBuffer(YRTDevice dev, YRTHandle camera, YRTHandle scene, YRTH
   auto S = D.get<SceneObj>(scene, "scene");
   auto F = D.get<FrameBufferObj>(framebuffer, "framebuffer");
   if (!C || !S || !F) throw std::runtime_error("yrtDenoiseFrameBuffer: null handle");
-  D.denoise(*C, *S, *F, dp);
+  D.denoise({C.get()}, *S, {F.get()}, dp, false, "yrtDenoiseFrameBuffer");
   return 0;
   DEV_END(-1)
 }
@@ -830,7 +827,7 @@ int yrtDenoiseCube(YRTDevice dev, const YRTHandle* cameras, int numFrames, YRTHa
   }
   if (W > YRT_CUBE_MAX_WIDTH) throw std::runtime_error("yrtDenoiseCube: faces wider than 16384 pixels");
   if (!D.gpu) throw std::runtime_error("yrtDenoiseCube: host-only device (created with parms \"host\")");
-  D.denoiseCube(C, *S, F, dp);
+  D.denoise(C, *S, F, dp, true, "yrtDenoiseCube");
   return 0;
   DEV_END(-1)
 }

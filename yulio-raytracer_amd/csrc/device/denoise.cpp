@@ -5,22 +5,26 @@
 
 namespace yrt {
 
-void Device::guides(CameraObj& C, SceneObj& S, int W, int H, const char* what, bool albedo) {
+// The scene and size checks of the whole stage live here: every entry point comes through.
+void Device::guides(const std::vector<CameraObj*>& C, SceneObj& S, int W, int H, const char* what, bool albedo) {
   if (!S.gpu) throw std::runtime_error(std::string(what) + ": scene not committed");
   if (S.gpu->device != hipDevice) throw std::runtime_error(std::string(what) + ": scene committed on another HIP device");
+  const int faces = (int)C.size();
   // one thread per pixel in 64-lane blocks: the grid stays far inside 2^31 blocks
-  if ((long long)W * H > (1ll << 30)) throw std::runtime_error(std::string(what) + ": more than 2^30 pixels");
+  if ((long long)faces * W * H > (1ll << 30)) throw std::runtime_error(std::string(what) + ": more than 2^30 pixels");
   HIP_CHECK(hipSetDevice(hipDevice));
   GpuCtx& g = *ctx[0];
-  const size_t bytes = (size_t)W * H * sizeof(float4);
-  g.dCam.alloc(sizeof(GpuCamera));
+  const size_t bytes = (size_t)faces * W * H * sizeof(float4);
+  std::vector<GpuCamera> cams(faces);
+  for (int k = 0; k < faces; ++k) cams[k] = C[k]->cam;
+  g.dCam.alloc(cams.size() * sizeof(GpuCamera));
   g.dGuidePos.alloc(bytes);
   g.dGuideNrm.alloc(bytes);
   if (albedo) g.dGuideAlbedo.alloc(bytes);
-  HIP_CHECK(hipMemcpyAsync(g.dCam.p, &C.cam, sizeof(GpuCamera), hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemcpyAsync(g.dCam.p, cams.data(), cams.size() * sizeof(GpuCamera), hipMemcpyHostToDevice, stream));
   evGuides.time(kernelTiming, stream, [&] {
-    launch_guides(S.gpu->view, g.dCam.as<GpuCamera>(), W, H, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(),
-                  albedo ? g.dGuideAlbedo.as<float4>() : nullptr, stream);
+    launch_guides(S.gpu->view, g.dCam.as<GpuCamera>(), faces, W, H, g.dGuidePos.as<float4>(),
+                  g.dGuideNrm.as<float4>(), albedo ? g.dGuideAlbedo.as<float4>() : nullptr, stream);
   });
   HIP_CHECK(hipGetLastError());
 }
@@ -46,35 +50,60 @@ Device::FilterFrame Device::filter_frame(FrameBufferObj& F, int id) {
   return ff;
 }
 
-// yrtDenoiseFrameBuffer: guides, c_0 = the frame as it stands, `iterations` a-trous passes
-// ping-ponging between two float4 frames, the last one storing into the frame's own format.
-// An RGB8 / RGB_FLOAT32 frame still in ctx[0]'s frame block is filtered there (the block holds
-// exactly those layouts; the next rtMapFrameBuffer reads the filtered frame back). The RGBA
-// formats exist on the host only (fb_read_back converts the block's RGB floats), so such a frame
-// is read back first and, like any frame already mapped or rendered into user pointers,
-// uploaded from the host pixels, filtered and copied back into them.
-// demodulate: the guide pass also renders the first-hit albedo, the load divides the frame by the
+// yrtDenoiseFrameBuffer / yrtDenoiseCube: the filter over a surface of C.size() frames of one size
+// and format, F[k] seen through C[k]: one frame whose taps stop at its border, or (wrap) the 6 or
+// 12 square faces of a stereo cube in slot order k = eye * 6 + cubeFaceIndex % 6, which the caller
+// has validated, whose taps cross the cube's edges. Guides, c_0 = the frames as they stand,
+// `iterations` a-trous passes ping-ponging between two float4 [face][H][W] arrays, the last one
+// storing into the frames' own format, one launch per stage.
+// Each frame is filtered where it lives (filter_frame). An RGB8 / RGB_FLOAT32 frame still in
+// ctx[0]'s frame block is filtered there (the block holds exactly those layouts; the next
+// rtMapFrameBuffer reads the filtered frame back). The RGBA formats exist on the host only
+// (fb_read_back converts the block's RGB floats), so such a frame is read back first and, like any
+// frame already mapped or rendered into user pointers, uploaded from the host pixels into a
+// 16-byte-aligned slot of dFilterFb, filtered and copied back into them.
+// demodulate: the guide pass also renders the first-hit albedo, the load divides the frames by the
 // modulation max(albedo, albedoFloor) ^ albedoPower and the last iteration multiplies it back
-// (k_atrous<true>); clear, the kernels are the <false> instantiations: no albedo, today's arithmetic.
-void Device::denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDenoiseParams& p) {
-  if (!S.gpu) throw std::runtime_error("yrtDenoiseFrameBuffer: scene not committed");
+// (k_atrous<true>); clear, the kernels are the <false> instantiations: no albedo.
+void Device::denoise(const std::vector<CameraObj*>& C, SceneObj& S, const std::vector<FrameBufferObj*>& F,
+                     const YRTDenoiseParams& p, bool wrap, const char* what) {
+  // also of a call that filters nothing (below), which never reaches the guide pass
+  if (!S.gpu) throw std::runtime_error(std::string(what) + ": scene not committed");
   if (p.iterations == 0) return;
-  const int W = F.width, H = F.height, id = F.cur;
+  const int faces = (int)C.size(), W = F[0]->width, H = F[0]->height;
   if (W < 1 || H < 1) return;
   const bool demod = p.demodulate != 0;
-  guides(C, S, W, H, "yrtDenoiseFrameBuffer", demod);
+  guides(C, S, W, H, what, demod);
   GpuCtx& g = *ctx[0];
-  const FilterFrame ff = filter_frame(F, id);
-  const bool inBlock = ff.inBlock;
-  const size_t fbBytes = F.stride * (size_t)H;
-  FrameIO io = ff.io;
-  if (!inBlock) {
-    HIP_CHECK(hipSetDevice(hipDevice));
-    g.dFilterFb.alloc(fbBytes);
-    HIP_CHECK(hipMemcpyAsync(g.dFilterFb.p, F.buffer(id), fbBytes, hipMemcpyHostToDevice, stream));
-    io.pixels = g.dFilterFb.p;
+
+  // the frames: in the block, or uploaded side by side into dFilterFb
+  const size_t fbBytes = F[0]->stride * (size_t)H, fbSlot = (fbBytes + 15) / 16 * 16;
+  std::vector<FrameIO> ios(faces);
+  std::vector<int> ids(faces);
+  std::vector<char> onHost(faces, 0);
+  size_t uploads = 0;
+  for (int k = 0; k < faces; ++k) {
+    ids[k] = F[k]->cur;
+    const FilterFrame ff = filter_frame(*F[k], ids[k]);
+    ios[k] = ff.io;
+    if (!ff.inBlock) {
+      onHost[k] = 1;
+      ++uploads;
+    }
   }
-  const size_t frameBytes = (size_t)W * H * sizeof(float4);
+  HIP_CHECK(hipSetDevice(hipDevice));  // a read-back may have selected the frame's device
+  if (uploads) {
+    g.dFilterFb.alloc(uploads * fbSlot);
+    size_t u = 0;
+    for (int k = 0; k < faces; ++k) {
+      if (!onHost[k]) continue;
+      ios[k].pixels = (char*)g.dFilterFb.p + u++ * fbSlot;
+      HIP_CHECK(hipMemcpyAsync(ios[k].pixels, F[k]->buffer(ids[k]), fbBytes, hipMemcpyHostToDevice, stream));
+    }
+  }
+  g.dFaceIo.alloc(ios.size() * sizeof(FrameIO));
+  HIP_CHECK(hipMemcpyAsync(g.dFaceIo.p, ios.data(), ios.size() * sizeof(FrameIO), hipMemcpyHostToDevice, stream));
+  const size_t frameBytes = (size_t)faces * W * H * sizeof(float4);
   g.dFilter[0].alloc(frameBytes);
   if (p.iterations > 1) g.dFilter[1].alloc(frameBytes);
   Demodulation dm;
@@ -86,26 +115,28 @@ void Device::denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDeno
     dm.albedoPower = p.albedoPower;
   }
   evFilter.time(kernelTiming, stream, [&] {
-    launch_atrous_load(io, g.dFilter[0].as<float4>(), dm, stream);
+    launch_atrous_load(g.dFaceIo.as<FrameIO>(), faces, W, H, g.dFilter[0].as<float4>(), dm, stream);
     AtrousParams ap;
     memset(&ap, 0, sizeof(ap));
     ap.width = W;
     ap.height = H;
     ap.sigmaNormal = p.sigmaNormal;
     ap.sigmaPosition = p.sigmaPosition;
-    const FrameIO none{nullptr, 0, W, H, 0, 0};
     for (int i = 0; i < p.iterations; ++i) {
       const bool last = i + 1 == p.iterations;
       ap.step = 1 << i;
       // sigmaColor_i = sigmaColor 2^-i (Dammertz et al.): the colour weight tightens as the taps spread
       const float sc = p.sigmaColor > 0.f ? p.sigmaColor / (float)(1 << i) : 0.f;
       ap.rcpSigmaColor2 = sc > 0.f ? 1.0f / (sc * sc) : 0.f;
-      launch_atrous(ap, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(), g.dFilter[i & 1].as<float4>(),
-                    last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(), last ? io : none, dm.mod4, stream);
+      launch_atrous(ap, faces, wrap, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(), g.dFilter[i & 1].as<float4>(),
+                    last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(), last ? g.dFaceIo.as<FrameIO>() : nullptr,
+                    dm.mod4, stream);
     }
   });
   HIP_CHECK(hipGetLastError());
-  if (!inBlock) HIP_CHECK(hipMemcpyAsync(F.buffer(id), g.dFilterFb.p, fbBytes, hipMemcpyDeviceToHost, stream));
+  for (int k = 0; k < faces; ++k)
+    if (onHost[k])
+      HIP_CHECK(hipMemcpyAsync(F[k]->buffer(ids[k]), ios[k].pixels, fbBytes, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream));
   evGuides.read(msGuides);
   evFilter.read(msFilter);
@@ -174,101 +205,6 @@ std::string cube_cameras_defect(const GpuCamera& cam) {
     }
   }
   return "";
-}
-
-// yrtDenoiseCube: Device::denoise over `faces` (6 or 12) square W x W frames in one launch per
-// stage. C[k], F[k]: the camera and framebuffer of slot k = eye * 6 + cubeFaceIndex % 6 (the
-// caller has validated and ordered them). The guide and filter frames are [slot][W][W] arrays;
-// each frame is filtered where it lives (filter_frame): the frames that live on the host share one
-// upload buffer and are copied back after the last iteration.
-void Device::denoiseCube(const std::vector<CameraObj*>& C, SceneObj& S, const std::vector<FrameBufferObj*>& F,
-                         const YRTDenoiseParams& p) {
-  const char* what = "yrtDenoiseCube";
-  if (!S.gpu) throw std::runtime_error(std::string(what) + ": scene not committed");
-  if (S.gpu->device != hipDevice) throw std::runtime_error(std::string(what) + ": scene committed on another HIP device");
-  if (p.iterations == 0) return;
-  const int faces = (int)C.size(), W = F[0]->width;
-  // one thread per pixel in 64-lane blocks: the grid stays far inside 2^31 blocks
-  if ((long long)faces * W * W > (1ll << 30)) throw std::runtime_error(std::string(what) + ": more than 2^30 pixels");
-  const bool demod = p.demodulate != 0;
-  HIP_CHECK(hipSetDevice(hipDevice));
-  GpuCtx& g = *ctx[0];
-  const size_t frameBytes = (size_t)faces * W * W * sizeof(float4);
-  std::vector<GpuCamera> cams(faces);
-  for (int k = 0; k < faces; ++k) cams[k] = C[k]->cam;
-  g.dCubeCams.alloc(cams.size() * sizeof(GpuCamera));
-  g.dGuidePos.alloc(frameBytes);
-  g.dGuideNrm.alloc(frameBytes);
-  if (demod) g.dGuideAlbedo.alloc(frameBytes);
-  HIP_CHECK(hipMemcpyAsync(g.dCubeCams.p, cams.data(), cams.size() * sizeof(GpuCamera), hipMemcpyHostToDevice, stream));
-  evGuides.time(kernelTiming, stream, [&] {
-    launch_guides_cube(S.gpu->view, g.dCubeCams.as<GpuCamera>(), faces, W, g.dGuidePos.as<float4>(),
-                       g.dGuideNrm.as<float4>(), demod ? g.dGuideAlbedo.as<float4>() : nullptr, stream);
-  });
-  HIP_CHECK(hipGetLastError());
-
-  // the frames: in the block, or uploaded side by side (16-byte aligned) into dFilterFb
-  const size_t fbBytes = F[0]->stride * (size_t)W, fbSlot = (fbBytes + 15) / 16 * 16;
-  std::vector<FrameIO> ios(faces);
-  std::vector<int> ids(faces);
-  std::vector<char> onHost(faces, 0);
-  size_t uploads = 0;
-  for (int k = 0; k < faces; ++k) {
-    ids[k] = F[k]->cur;
-    const FilterFrame ff = filter_frame(*F[k], ids[k]);
-    ios[k] = ff.io;
-    if (!ff.inBlock) {
-      onHost[k] = 1;
-      ++uploads;
-    }
-  }
-  HIP_CHECK(hipSetDevice(hipDevice));  // a read-back may have selected the frame's device
-  if (uploads) {
-    g.dFilterFb.alloc(uploads * fbSlot);
-    size_t u = 0;
-    for (int k = 0; k < faces; ++k) {
-      if (!onHost[k]) continue;
-      ios[k].pixels = (char*)g.dFilterFb.p + u++ * fbSlot;
-      HIP_CHECK(hipMemcpyAsync(ios[k].pixels, F[k]->buffer(ids[k]), fbBytes, hipMemcpyHostToDevice, stream));
-    }
-  }
-  g.dCubeIo.alloc(ios.size() * sizeof(FrameIO));
-  HIP_CHECK(hipMemcpyAsync(g.dCubeIo.p, ios.data(), ios.size() * sizeof(FrameIO), hipMemcpyHostToDevice, stream));
-  g.dFilter[0].alloc(frameBytes);
-  if (p.iterations > 1) g.dFilter[1].alloc(frameBytes);
-  Demodulation dm;
-  if (demod) {
-    g.dFilterMod.alloc(frameBytes);
-    dm.albedo4 = g.dGuideAlbedo.as<float4>();
-    dm.mod4 = g.dFilterMod.as<float4>();
-    dm.albedoFloor = p.albedoFloor;
-    dm.albedoPower = p.albedoPower;
-  }
-  evFilter.time(kernelTiming, stream, [&] {
-    launch_atrous_load_cube(g.dCubeIo.as<FrameIO>(), faces, W, g.dFilter[0].as<float4>(), dm, stream);
-    AtrousParams ap;
-    memset(&ap, 0, sizeof(ap));
-    ap.width = W;
-    ap.height = W;
-    ap.sigmaNormal = p.sigmaNormal;
-    ap.sigmaPosition = p.sigmaPosition;
-    for (int i = 0; i < p.iterations; ++i) {
-      const bool last = i + 1 == p.iterations;
-      ap.step = 1 << i;
-      const float sc = p.sigmaColor > 0.f ? p.sigmaColor / (float)(1 << i) : 0.f;  // as Device::denoise
-      ap.rcpSigmaColor2 = sc > 0.f ? 1.0f / (sc * sc) : 0.f;
-      launch_atrous_cube(ap, faces, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(), g.dFilter[i & 1].as<float4>(),
-                         last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(), last ? g.dCubeIo.as<FrameIO>() : nullptr,
-                         dm.mod4, stream);
-    }
-  });
-  HIP_CHECK(hipGetLastError());
-  for (int k = 0; k < faces; ++k)
-    if (onHost[k])
-      HIP_CHECK(hipMemcpyAsync(F[k]->buffer(ids[k]), ios[k].pixels, fbBytes, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipStreamSynchronize(stream));
-  evGuides.read(msGuides);
-  evFilter.read(msFilter);
 }
 
 }  // namespace yrt

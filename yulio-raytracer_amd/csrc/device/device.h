@@ -3,7 +3,7 @@
 //   device.cpp         Device's ray queries, frame read-back, scene commit
 //   render.cpp         Device::render (the frame job), Device::render_shard (one device's share)
 //   render_job.{h,cpp} the batch plan and the wavefront lane scheduler render_shard runs
-//   denoise.cpp        Device::guides, Device::denoise, Device::denoiseCube and its cube check
+//   denoise.cpp        Device::guides, Device::denoise (a frame or a cube's faces), the cube-camera check
 //   gather_device.cpp  Device::gather_local, Device::gather_process
 //   api_objects.cpp, api_tools.cpp  the extern "C" entry points (include/yrt_device.h)
 #pragma once
@@ -91,11 +91,10 @@ struct GpuCtx {
   Lane lanes[kMaxLanes];
   int numLanes = kDefaultLanes;
   DevBuf dRp, dCam, dPixelSets, dAccu, dCount, dSpill, dSlab, dDirect;
-  // denoise (yrtRenderGuides / yrtDenoiseFrameBuffer): the guide frames, the filter's two
-  // ping-pong float4 frames and the upload of a frame that lives in host pixels
-  DevBuf dGuidePos, dGuideNrm, dGuideAlbedo, dFilter[2], dFilterMod, dFilterFb;
-  // yrtDenoiseCube: the faces' camera records and their FrameIO records
-  DevBuf dCubeCams, dCubeIo;
+  // denoise (yrtRenderGuides / yrtDenoiseFrameBuffer / yrtDenoiseCube), per face of the surface:
+  // the guide frames, the filter's two ping-pong float4 frames, the modulation, the uploads of the
+  // frames that live in host pixels and the FrameIO records; the cameras go to dCam
+  DevBuf dGuidePos, dGuideNrm, dGuideAlbedo, dFilter[2], dFilterMod, dFilterFb, dFaceIo;
   // The frames a job renders into (float RGB and RGB8 rows, frame-major). On the primary
   // device a job's framebuffers keep a reference to their block until rtMapFrameBuffer reads
   // them back, so the next job renders into the spare (or a fresh) block meanwhile.
@@ -364,23 +363,24 @@ class Device {
   void fail_proc_gather();
   void intersect(SceneObj& S, const float* org4, const float* dir4, uint32_t n, float* hit4, int32_t* occ,
                  hipStream_t st);
-  // the first-hit guide frames of a W x H view of C in ctx[0]'s dGuidePos / dGuideNrm (enqueued
-  // on the primary stream); albedo: the same pass also fills dGuideAlbedo (k_guides<true>)
-  void guides(CameraObj& C, SceneObj& S, int W, int H, const char* what, bool albedo = false);
+  // the first-hit guide frames of the W x H views of C (one frame: one camera) as [face][H][W]
+  // arrays in ctx[0]'s dGuidePos / dGuideNrm (enqueued on the primary stream); albedo: the same
+  // pass also fills dGuideAlbedo (k_guides<true>). Checks the scene and the pixel count.
+  void guides(const std::vector<CameraObj*>& C, SceneObj& S, int W, int H, const char* what, bool albedo);
   // yrtSetKernelTiming: HIP-event times of the last guide pass and the last filter (its load and
   // iterations), yrtGetDenoiseTimes
   EvPair evGuides, evFilter;
   float msGuides = 0.f, msFilter = 0.f;
-  void denoise(CameraObj& C, SceneObj& S, FrameBufferObj& F, const YRTDenoiseParams& p);
+  // the filter over the frames F[k] of one size and format seen through C[k], in place: one frame,
+  // or (wrap) the validated slots k = eye * 6 + face of a stereo cube filtered as one surface
+  void denoise(const std::vector<CameraObj*>& C, SceneObj& S, const std::vector<FrameBufferObj*>& F,
+               const YRTDenoiseParams& p, bool wrap, const char* what);
   // where buffer `id` of F lives for the filter: in this device's frame block, or on the host
   struct FilterFrame {
     FrameIO io;
     bool inBlock;
   };
   FilterFrame filter_frame(FrameBufferObj& F, int id);
-  // yrtDenoiseCube over validated slots k = eye * 6 + face: C[k] through F[k]
-  void denoiseCube(const std::vector<CameraObj*>& C, SceneObj& S, const std::vector<FrameBufferObj*>& F,
-                   const YRTDenoiseParams& p);
 };
 
 // yrtDenoiseCube's host check: empty when the six faces of a committed stereo camera are the ideal

@@ -15,24 +15,22 @@ __device__ __forceinline__ size_t fb_channel(const FrameIO& io, int x, int y) {
   return (size_t)y * io.rowStride + (size_t)x * io.pixStride;
 }
 
-// c_0 of the filter: the framebuffer's pixels as float4 (8-bit channels as byte / 255).
+// c_0 of the filter: the framebuffer's pixels as float4 (8-bit channels as byte / 255), one
+// width x height frame per face: blockIdx.y is the face, its pixels are those of faceIo[face] and
+// dst, albedo4 and mod4 are [face][height][width] arrays.
 // DEMOD (YRTDenoiseParams::demodulate): a hit pixel's modulation m = max(albedo, floor) ^ power
 // per channel goes to mod4 and the filter's input is d_0 = c_0 / m (IEEE divisions); a miss
 // pixel, which the filter neither reads nor writes, keeps c_0 and gets m = 1.
-// CUBE (yrtDenoiseCube): dst, albedo4 and mod4 are [face][W][W] arrays, blockIdx.y is the face
-// and face f's pixels are those of faceIo[f] (frames of io's size).
-template <bool DEMOD, bool CUBE = false>
-__global__ __launch_bounds__(YRT_BLOCK) void k_atrous_load(FrameIO io, float4* __restrict__ dst,
+template <bool DEMOD>
+__global__ __launch_bounds__(YRT_BLOCK) void k_atrous_load(const FrameIO* __restrict__ faceIo, int width, int height,
+                                                           float4* __restrict__ dst,
                                                            const float4* __restrict__ albedo4, float albedoFloor,
-                                                           float albedoPower, float4* __restrict__ mod4,
-                                                           const FrameIO* __restrict__ faceIo) {
+                                                           float albedoPower, float4* __restrict__ mod4) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)io.width * io.height) return;
-  const int y = (int)(i / io.width), x = (int)(i - (long long)y * io.width);
-  if constexpr (CUBE) {
-    i += (long long)blockIdx.y * io.width * io.height;
-    io = faceIo[blockIdx.y];
-  }
+  if (i >= (long long)width * height) return;
+  const int y = (int)(i / width), x = (int)(i - (long long)y * width);
+  i += (long long)blockIdx.y * width * height;
+  const FrameIO io = faceIo[blockIdx.y];
   const size_t o = fb_channel(io, x, y);
   float4 c;
   if (io.bytes) {
@@ -64,27 +62,27 @@ __device__ __forceinline__ float atrous_h(int d) { return d == 0 ? 0.375f : (d =
 //   w_n = max(0, n_p . n_q) ^ sigmaNormal
 //   w_x = exp(-|n_p . (x_q - x_p)| / (sigmaPosition t_p))
 //   w_c = exp(-|c_p - c_q|^2 / sigmaColor_i^2)                  (rcpSigmaColor2 = 0: off)
-// Taps outside the image or on a miss are skipped; the centre tap weighs h(0)^2 exactly. The
-// mean is taken as c_p + sum w (c_q - c_p) / sum w, so a constant frame stays what it is.
-// A miss pixel is not written. The last iteration (out, or CUBE's faceOut, != null) stores into the framebuffer:
-// floats as they are, bytes as k_resolve_pixels quantizes them; alpha and row padding are
-// not touched. DEMOD: the frames hold the demodulated signal d (k_atrous_load), every weight
-// acts on d, and the last iteration stores d_n m with the modulation of mod4.
-// CUBE (yrtDenoiseCube): the frames are [face][W][W] arrays, six faces per eye in cubeFaceIndex
-// order, and blockIdx.y is the face; a tap that leaves its face reads the pixel yrt_cube_tap
-// names on a neighbour of the same eye (a corner tap is skipped), with the same weights; the last
-// iteration stores face f's pixels into faceOut[f].
-template <bool DEMOD, bool CUBE = false>
+// Taps on a miss are skipped; the centre tap weighs h(0)^2 exactly. The mean is taken as
+// c_p + sum w (c_q - c_p) / sum w, so a constant frame stays what it is. A miss pixel is not
+// written. The frames are [face][height][width] arrays and blockIdx.y is the face. A tap that
+// leaves its face is skipped, or, with WRAP (yrtDenoiseCube: square faces, six per eye in
+// cubeFaceIndex order), reads the pixel yrt_cube_tap names on a neighbour of the same eye (a
+// corner tap is skipped), with the same weights. The last iteration (faceOut != null) stores face
+// f's pixels into the framebuffer faceOut[f]: floats as they are, bytes as k_resolve_pixels
+// quantizes them; alpha and row padding are not touched. DEMOD: the frames hold the demodulated
+// signal d (k_atrous_load), every weight acts on d, and the last iteration stores d_n m with the
+// modulation of mod4.
+template <bool DEMOD, bool WRAP>
 __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const float4* __restrict__ pos4,
                                                       const float4* __restrict__ nrm4, const float4* __restrict__ src,
-                                                      float4* __restrict__ dst, FrameIO out,
-                                                      const float4* __restrict__ mod4,
+                                                      float4* __restrict__ dst, const float4* __restrict__ mod4,
                                                       const FrameIO* __restrict__ faceOut) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)ap.width * ap.height) return;
   const int y = (int)(i / ap.width), x = (int)(i - (long long)y * ap.width);
-  const int face = CUBE ? (int)blockIdx.y : 0;
-  if constexpr (CUBE) i += (long long)face * ap.width * ap.height;
+  const int face = (int)blockIdx.y;
+  const size_t base = (size_t)face * ap.width * ap.height;  // of this face's frame
+  i += (long long)base;
   const float INF = __int_as_float(0x7f800000);
   const float4 pp = pos4[i];
   if (!(pp.w < INF)) return;
@@ -95,18 +93,18 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const flo
   float wsum = atrous_h(0) * atrous_h(0);
   for (int dy = -2; dy <= 2; ++dy) {
     const long long qy = (long long)y + (long long)dy * ap.step;
-    if (!CUBE && (qy < 0 || qy >= ap.height)) continue;
+    if (!WRAP && (qy < 0 || qy >= ap.height)) continue;
     for (int dx = -2; dx <= 2; ++dx) {
       const long long qx = (long long)x + (long long)dx * ap.step;
       size_t j;
-      if constexpr (CUBE) {
+      if constexpr (WRAP) {
         if (dx == 0 && dy == 0) continue;
         int g, tx, ty;  // the host keeps W and the step inside yrt_cube_tap's range
         if (yrt_cube_tap(ap.width, face % 6, (int)qx, (int)qy, &g, &tx, &ty) != 1) continue;
         j = ((size_t)(face - face % 6 + g) * ap.height + (size_t)ty) * ap.width + (size_t)tx;
       } else {
         if (qx < 0 || qx >= ap.width || (dx == 0 && dy == 0)) continue;
-        j = (size_t)qy * ap.width + (size_t)qx;
+        j = base + (size_t)qy * ap.width + (size_t)qx;
       }
       const float4 pq = pos4[j];
       if (!(pq.w < INF)) continue;
@@ -121,7 +119,7 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const flo
     }
   }
   V3 c = cp + sum * (1.0f / wsum);
-  if (CUBE ? !faceOut : !out.pixels) {
+  if (!faceOut) {
     dst[i] = make_float4(c.x, c.y, c.z, 0.f);
     return;
   }
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_atrous(AtrousParams ap, const flo
     const float4 m = mod4[i];
     c = c * v3(m.x, m.y, m.z);
   }
-  if constexpr (CUBE) out = faceOut[face];
+  const FrameIO out = faceOut[face];
   const size_t o = fb_channel(out, x, y);
   if (out.bytes) {
     uint8_t* p = (uint8_t*)out.pixels + o;

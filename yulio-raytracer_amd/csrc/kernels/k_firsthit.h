@@ -110,20 +110,17 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) void k_pick(SceneView sv, const Gp
 // of R over the diffuse-reflection components; (1, 1, 1) where there is none, where the sum is
 // 0 and on a light primitive. Off the render loop: its component set may live
 // in scratch.
-// CUBE (yrtDenoiseCube): blockIdx.y is the face, camp holds one camera record per face, the
-// frames are [face][height][width] arrays and face f's pixels are what the plain kernel stores
-// for camp[f].
-template <bool ALBEDO, bool CUBE = false>
+// One view per face (a single frame is one face): blockIdx.y is the face, camp[face] its camera
+// and the frames are [face][height][width] arrays.
+template <bool ALBEDO>
 __global__ __launch_bounds__(YRT_TRACE_BLOCK) void k_guides(SceneView sv, const GpuCamera* camp, int width, int height,
                                                             float4* __restrict__ pos4, float4* __restrict__ nrm4,
                                                             float4* __restrict__ albedo4) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)width * height) return;
   const int y = (int)(i / width), x = (int)(i - (long long)y * width);
-  if constexpr (CUBE) {
-    i += (long long)blockIdx.y * width * height;
-    camp += blockIdx.y;
-  }
+  i += (long long)blockIdx.y * width * height;
+  camp += blockIdx.y;
   V3 org, dir;
   camera_ray(*camp, (float(x) + 0.5f) / float(width), (float(y) + 0.5f) / float(height), org, dir);
   const Hit h = closest_hit(sv.qnodes, sv.tris, org, dir, 0.f, __int_as_float(0x7f800000));

@@ -380,82 +380,32 @@ void launch_pick(const SceneView& sv, const GpuCamera* cam, float x, float y, fl
   hipLaunchKernelGGL(k_pick, dim3(1), dim3(YRT_TRACE_BLOCK), 0, s, sv, cam, x, y, out);
 }
 
-void launch_guides(const SceneView& sv, const GpuCamera* cam, int width, int height, float4* pos4, float4* nrm4,
-                   float4* albedo4, hipStream_t s) {
+void launch_guides(const SceneView& sv, const GpuCamera* cams, int faces, int width, int height, float4* pos4,
+                   float4* nrm4, float4* albedo4, hipStream_t s) {
   const long long n = (long long)width * height;
-  if (n <= 0) return;
-  const dim3 grid((unsigned)((n + YRT_TRACE_BLOCK - 1) / YRT_TRACE_BLOCK));
-  if (albedo4)
-    hipLaunchKernelGGL(k_guides<true>, grid, dim3(YRT_TRACE_BLOCK), 0, s, sv, cam, width, height, pos4, nrm4, albedo4);
-  else
-    hipLaunchKernelGGL(k_guides<false>, grid, dim3(YRT_TRACE_BLOCK), 0, s, sv, cam, width, height, pos4, nrm4,
-                       (float4*)nullptr);
-}
-
-void launch_guides_cube(const SceneView& sv, const GpuCamera* cams, int faces, int width, float4* pos4, float4* nrm4,
-                        float4* albedo4, hipStream_t s) {
-  const long long n = (long long)width * width;
   if (n <= 0 || faces <= 0) return;
   const dim3 grid((unsigned)((n + YRT_TRACE_BLOCK - 1) / YRT_TRACE_BLOCK), (unsigned)faces);
-  if (albedo4)
-    hipLaunchKernelGGL((k_guides<true, true>), grid, dim3(YRT_TRACE_BLOCK), 0, s, sv, cams, width, width, pos4, nrm4,
-                       albedo4);
-  else
-    hipLaunchKernelGGL((k_guides<false, true>), grid, dim3(YRT_TRACE_BLOCK), 0, s, sv, cams, width, width, pos4, nrm4,
-                       (float4*)nullptr);
+  hipLaunchKernelGGL(albedo4 ? k_guides<true> : k_guides<false>, grid, dim3(YRT_TRACE_BLOCK), 0, s, sv, cams, width,
+                     height, pos4, nrm4, albedo4);
 }
 
-void launch_atrous_load(const FrameIO& io, float4* dst, const Demodulation& dm, hipStream_t s) {
-  const long long n = (long long)io.width * io.height;
-  if (n <= 0) return;
-  const dim3 grid((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK));
-  if (dm.mod4)
-    hipLaunchKernelGGL(k_atrous_load<true>, grid, dim3(YRT_BLOCK), 0, s, io, dst, dm.albedo4, dm.albedoFloor,
-                       dm.albedoPower, dm.mod4, (const FrameIO*)nullptr);
-  else
-    hipLaunchKernelGGL(k_atrous_load<false>, grid, dim3(YRT_BLOCK), 0, s, io, dst, (const float4*)nullptr, 0.f, 0.f,
-                       (float4*)nullptr, (const FrameIO*)nullptr);
-}
-
-void launch_atrous_load_cube(const FrameIO* faceIo, int faces, int width, float4* dst, const Demodulation& dm,
-                             hipStream_t s) {
-  const long long n = (long long)width * width;
+void launch_atrous_load(const FrameIO* faceIo, int faces, int width, int height, float4* dst, const Demodulation& dm,
+                        hipStream_t s) {
+  const long long n = (long long)width * height;
   if (n <= 0 || faces <= 0) return;
   const dim3 grid((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK), (unsigned)faces);
-  const FrameIO size{nullptr, 0, width, width, 0, 0};  // the faces' own records come from faceIo
-  if (dm.mod4)
-    hipLaunchKernelGGL((k_atrous_load<true, true>), grid, dim3(YRT_BLOCK), 0, s, size, dst, dm.albedo4, dm.albedoFloor,
-                       dm.albedoPower, dm.mod4, faceIo);
-  else
-    hipLaunchKernelGGL((k_atrous_load<false, true>), grid, dim3(YRT_BLOCK), 0, s, size, dst, (const float4*)nullptr,
-                       0.f, 0.f, (float4*)nullptr, faceIo);
+  hipLaunchKernelGGL(dm.mod4 ? k_atrous_load<true> : k_atrous_load<false>, grid, dim3(YRT_BLOCK), 0, s, faceIo, width,
+                     height, dst, dm.albedo4, dm.albedoFloor, dm.albedoPower, dm.mod4);
 }
 
-void launch_atrous(const AtrousParams& ap, const float4* pos4, const float4* nrm4, const float4* src, float4* dst,
-                   const FrameIO& out, const float4* mod4, hipStream_t s) {
-  const long long n = (long long)ap.width * ap.height;
-  if (n <= 0) return;
-  const dim3 grid((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK));
-  if (mod4)
-    hipLaunchKernelGGL(k_atrous<true>, grid, dim3(YRT_BLOCK), 0, s, ap, pos4, nrm4, src, dst, out, mod4,
-                       (const FrameIO*)nullptr);
-  else
-    hipLaunchKernelGGL(k_atrous<false>, grid, dim3(YRT_BLOCK), 0, s, ap, pos4, nrm4, src, dst, out,
-                       (const float4*)nullptr, (const FrameIO*)nullptr);
-}
-
-void launch_atrous_cube(const AtrousParams& ap, int faces, const float4* pos4, const float4* nrm4, const float4* src,
-                        float4* dst, const FrameIO* faceOut, const float4* mod4, hipStream_t s) {
+void launch_atrous(const AtrousParams& ap, int faces, bool wrap, const float4* pos4, const float4* nrm4,
+                   const float4* src, float4* dst, const FrameIO* faceOut, const float4* mod4, hipStream_t s) {
   const long long n = (long long)ap.width * ap.height;
   if (n <= 0 || faces <= 0) return;
   const dim3 grid((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK), (unsigned)faces);
-  const FrameIO none{nullptr, 0, ap.width, ap.height, 0, 0};
-  if (mod4)
-    hipLaunchKernelGGL((k_atrous<true, true>), grid, dim3(YRT_BLOCK), 0, s, ap, pos4, nrm4, src, dst, none, mod4,
-                       faceOut);
-  else
-    hipLaunchKernelGGL((k_atrous<false, true>), grid, dim3(YRT_BLOCK), 0, s, ap, pos4, nrm4, src, dst, none,
-                       (const float4*)nullptr, faceOut);
+  const auto kernel = mod4 ? (wrap ? k_atrous<true, true> : k_atrous<true, false>)
+                           : (wrap ? k_atrous<false, true> : k_atrous<false, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(YRT_BLOCK), 0, s, ap, pos4, nrm4, src, dst, mod4, faceOut);
 }
 
 void launch_debug_render(const SceneView& sv, const FrameView& fv, int maxDepth, int spp, int numTiles, float* fbFloat,

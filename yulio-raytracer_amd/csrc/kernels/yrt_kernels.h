@@ -229,14 +229,19 @@ void launch_pack_tiles(const float* fbFloat, const uint8_t* fbRGB8, const SlabLa
 void launch_unpack_tiles(const void* slab, float* fbFloat, uint8_t* fbRGB8, const SlabLayout& L, int numTiles,
                          hipStream_t s);
 void launch_pick(const SceneView& sv, const GpuCamera* cam, float x, float y, float4* out, hipStream_t s);
-// Denoise (yrtRenderGuides / yrtRenderAlbedo / yrtDenoiseFrameBuffer; k_firsthit.h, k_denoise.h). launch_guides:
-// the first-hit guide frames of a width x height view of `cam`, one thread per pixel:
+// Denoise (yrtRenderGuides / yrtRenderAlbedo / yrtDenoiseFrameBuffer / yrtDenoiseCube; k_firsthit.h,
+// k_denoise.h): one kernel family over a surface of `faces` width x height frames, one launch per
+// stage, the float4 frames being [face][height][width] arrays. A single frame is a surface of one
+// face whose taps stop at its border; a stereo cube is one of 6 or 12 square faces, six per eye in
+// cubeFaceIndex order, whose taps wrap onto the neighbouring face of the same eye
+// (common/yrt_cube_tap.h). cams, faceIo and faceOut are device arrays of one record per face.
+// launch_guides: the first-hit guide frames, face f seen through cams[f], one thread per pixel:
 // pos4 = (hit point, t), nrm4 = (viewer-facing shading normal, 1); misses (0, 0, 0, inf) and 0.
 // albedo4 != null: the same pass also stores (first-hit albedo, 1), misses 0 (k_guides<true>).
-void launch_guides(const SceneView& sv, const GpuCamera* cam, int width, int height, float4* pos4, float4* nrm4,
-                   float4* albedo4, hipStream_t s);
+void launch_guides(const SceneView& sv, const GpuCamera* cams, int faces, int width, int height, float4* pos4,
+                   float4* nrm4, float4* albedo4, hipStream_t s);
 // A framebuffer's pixels in device memory: float (bytes = 0) or 8-bit (bytes = 1) channels,
-// pixStride (3 or 4) per pixel, rows rowStride channels apart; pixels = null: none
+// pixStride (3 or 4) per pixel, rows rowStride channels apart
 struct FrameIO {
   void* pixels;
   size_t rowStride;
@@ -254,24 +259,14 @@ struct Demodulation {
   float4* mod4 = nullptr;
   float albedoFloor = 0.f, albedoPower = 0.f;
 };
-// c_0: the framebuffer's pixels as float4 (8-bit channels / 255); demodulated: c_0 / modulation
-void launch_atrous_load(const FrameIO& io, float4* dst, const Demodulation& dm, hipStream_t s);
-// one filter iteration src -> dst (float4 frames), or src -> the framebuffer `out` (the last one,
-// times the modulation mod4 when that is not null)
-void launch_atrous(const AtrousParams& ap, const float4* pos4, const float4* nrm4, const float4* src, float4* dst,
-                   const FrameIO& out, const float4* mod4, hipStream_t s);
-// The cube forms (yrtDenoiseCube): one launch over `faces` (6 or 12) square width x width frames,
-// six per eye in cubeFaceIndex order, the float4 frames being [face][width][width] arrays. cams
-// and faceIo are device arrays of one record per face; face f's guides are launch_guides' for
-// cams[f] and its pixels those of faceIo[f]. launch_atrous_cube: a tap that leaves its face reads
-// the neighbouring face of the same eye (common/yrt_cube_tap.h); faceOut != null: the last
-// iteration, stored into the faces' framebuffers.
-void launch_guides_cube(const SceneView& sv, const GpuCamera* cams, int faces, int width, float4* pos4, float4* nrm4,
-                        float4* albedo4, hipStream_t s);
-void launch_atrous_load_cube(const FrameIO* faceIo, int faces, int width, float4* dst, const Demodulation& dm,
-                             hipStream_t s);
-void launch_atrous_cube(const AtrousParams& ap, int faces, const float4* pos4, const float4* nrm4, const float4* src,
-                        float4* dst, const FrameIO* faceOut, const float4* mod4, hipStream_t s);
+// c_0: face f's pixels, those of faceIo[f], as float4 (8-bit channels / 255); demodulated:
+// c_0 / modulation
+void launch_atrous_load(const FrameIO* faceIo, int faces, int width, int height, float4* dst, const Demodulation& dm,
+                        hipStream_t s);
+// one filter iteration src -> dst (float4 frames), or, faceOut != null, src -> the faces'
+// framebuffers (the last one, times the modulation mod4 when that is not null); wrap: the cube's taps
+void launch_atrous(const AtrousParams& ap, int faces, bool wrap, const float4* pos4, const float4* nrm4,
+                   const float4* src, float4* dst, const FrameIO* faceOut, const float4* mod4, hipStream_t s);
 // BVH refit after faceCamera updates: rewrite triangles [firstTri, firstTri+numTris) (global
 // ids) from the vertex buffer in every leaf slot that references them (leafSlots[leafStart[g]
 // .. leafStart[g+1])), then refit one tree level of nodes (call deepest level first)
