@@ -479,6 +479,92 @@ def test_multi_device_shards_bit_exact(gpu_device, monkeypatch, replica):
         multi.close()
 
 
+def _all_buffers_scene(d):
+    """A few quads that leave none of the scene's optional device buffers empty: a mesh with
+    motions, a mesh with tangent arrays under BrushedMetal (which reads them), a MatteTextured quad
+    over an 8-bit image (texels and their footprint records), an HDRI light over a float image
+    (the float part of the pool, precomputed light samples) and a triangle light."""
+    from test_cpu_host import yrt_lookat
+    import denoise_albedo_ref as aref
+    F = np.float32
+    quad = np.array([[-300, 0, -300], [300, 0, -300], [300, 0, 300], [-300, 0, 300]], F)
+    wall = np.array([[-300, 0, 300], [300, 0, 300], [300, 400, 300], [-300, 400, 300]], F)
+    box = np.array([[-60, 40, -60], [60, 40, -60], [60, 40, 60], [-60, 40, 60]], F)
+    uv = np.array([[0, 0], [1, 0], [1, 1], [0, 1]], F)
+    idx = np.array([[0, 2, 1], [0, 3, 2]], np.int32)
+    c, s_ = np.cos(np.pi / 6), np.sin(np.pi / 6)
+    up, back = np.array([[0, 1, 0]] * 4, F), np.array([[0, 0, -1]] * 4, F)
+
+    def mesh(pos, nor, **more):
+        m = d.rtNewShape("trianglemesh")
+        arrays = [("positions", pos, "float3"), ("normals", nor, "float3"), ("texcoords", uv, "float2"),
+                  ("indices", idx, "int3")] + [(k, np.asarray(v, F), "float3") for k, v in more.items()]
+        for name, arr, typ in arrays:
+            d.rtSetArray(m, name, typ, d.rtNewData("immutable", arr), len(arr), arr.itemsize * arr.shape[1])
+        d.rtCommit(m)
+        return m
+
+    img8 = np.ascontiguousarray((aref.texture_image(8) * 256).astype(np.uint8))
+    matte = aref.material(d, "MatteTextured", textures=[("Kd", aref.texture(d, "bilinear", img8, "RGB8"))])
+    metal = aref.material(d, "BrushedMetal", [("reflectance", (0.9, 0.8, 0.6)), ("roughnessX", 0.02),
+                                              ("roughnessY", 0.5)])
+    grey = aref.material(d, "Matte", [("reflectance", (0.6, 0.6, 0.6))])
+    sky = np.linspace(0.2, 1.0, 8 * 4 * 3, dtype=F).reshape(4, 8, 3)
+    hdri = d.rtNewLight("hdrilight")
+    d.rtSetImage(hdri, "image", d.rtNewImage("RGB_FLOAT32", 8, 4, sky))
+    d.rtSetFloat3(hdri, "L", 0.5, 0.5, 0.6)
+    d.rtCommit(hdri)
+    tl = d.rtNewLight("trianglelight")
+    for n, v in (("v0", (-60, 200, -60)), ("v1", (60, 200, -60)), ("v2", (0, 200, 80)), ("L", (40, 38, 30))):
+        d.rtSetFloat3(tl, n, *v)
+    d.rtCommit(tl)
+    scene = d.rtNewScene("default")
+    prims = [d.rtNewShapePrimitive(mesh(quad, up, tangent_x=[[c, 0, s_]] * 4, tangent_y=[[-s_, 0, c]] * 4), metal),
+             d.rtNewShapePrimitive(mesh(wall, back), matte),
+             d.rtNewShapePrimitive(mesh(box, up, motions=[[80, 0, 0]] * 4), grey),
+             d.rtNewLightPrimitive(hdri), d.rtNewLightPrimitive(tl)]
+    for slot, p in enumerate(prims):
+        d.rtSetPrimitive(scene, slot, p)
+    d.rtCommit(scene)
+    cam = d.rtNewCamera("pinhole")
+    d.rtSetTransform(cam, "local2world", yrt_lookat((0, 250, -420), (0, 100, 0), (0, 1, 0)))
+    d.rtSetFloat1(cam, "angle", 60.0)
+    d.rtSetFloat1(cam, "aspectRatio", 1.0)
+    d.rtCommit(cam)
+    r = d.rtNewRenderer("pathtracer")
+    d.rtSetInt1(r, "maxDepth", 3)
+    d.rtSetInt1(r, "sampler.spp", 2)
+    d.rtSetFloat1(r, "tMaxShadowRay", 1e4)
+    d.rtCommit(r)
+    tm = d.rtNewToneMapper("default")
+    d.rtCommit(tm)
+    return r, cam, scene, tm, d.rtNewFrameBuffer("RGB_FLOAT32", 64, 64)
+
+
+def test_scene_replica_has_every_buffer(gpu_device, monkeypatch):
+    """The peer copy of a scene (replicate_gpu_scene) carries every buffer the kernels read:
+    with motions, triMotion, tangents, 8-bit and float texels, texQuads and both kinds of light
+    in use, the frame of two shards that render from a replica equals the one-device frame bit
+    for bit, and so does the count of closest-hit rays. (test_multi_device_shards_bit_exact's
+    scenes leave motions, triMotion and tangents empty.)"""
+    monkeypatch.setenv("YRT_FORCE_SCENE_REPLICA", "1")
+    multi = yrt.Device(devices=[0, 0])
+    try:
+        out = []
+        for d in (gpu_device, multi):
+            r, cam, scene, tm, fb = _all_buffers_scene(d)
+            pools = d.debug_texture_pools(scene)
+            # the pool has an 8-bit part (one uint32 of the footprint records per byte) and a float part
+            assert 0 < pools["quads"].size < pools["texels"].size
+            d.rtRenderFrame(r, cam, scene, tm, fb, 0)
+            out.append((d.framebuffer_array(fb, 64, 64, "RGB_FLOAT32").copy(), d.render_stats()["raysClosest"]))
+        assert np.isfinite(out[0][0]).all() and out[0][0].std() > 0
+        assert np.array_equal(out[0][0], out[1][0])
+        assert out[0][1] == out[1][1]
+    finally:
+        multi.close()
+
+
 def test_startrt_multi_device_equals_single(tmp_path, monkeypatch):
     """StartRT over YRT_DEVICES=0,0 (two logical shards of the GPU) writes the same strips as
     over one device."""

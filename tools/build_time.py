@@ -10,10 +10,12 @@
              kernel's order (oracle.count_visits; a CPU number), with --visits
   frame      wall time of a path-traced frame (C3: the view; C5: cube face 0), with --frames N
 
-    python tools/build_time.py [--host] [--scenes C3,C5,HF20] [--reps 3] [--visits] [--frames 5]
+    python tools/build_time.py [--host] [--scenes C3,C5,HF20] [--reps 3] [--visits] [--frames 5] [--tree CHECKOUT]
 
 Scenes: C3 (yrt.standin), C5 (yrt.frederick), HFn (a 2^n-triangle height field). --host runs the
-builders' host paths on the host-only device (morton's serial loop, builder 2).
+builders' host paths on the host-only device (morton's serial loop, builder 2). --tree: the built
+checkout whose library, package and test scenes are measured (default: this one), so that two
+builds are timed by the same script.
 """
 from __future__ import annotations
 
@@ -24,13 +26,6 @@ import time
 from pathlib import Path
 
 import numpy as np
-
-ROOT = Path(__file__).resolve().parent.parent
-for p in (ROOT, ROOT / "yulio-raytracer_amd", ROOT / "tests"):
-    sys.path.insert(0, str(p))
-
-import oracle  # noqa: E402
-import yrt  # noqa: E402
 
 BUILDERS = ("default", "morton")
 
@@ -116,7 +111,14 @@ def main():
     ap.add_argument("--frames", type=int, default=0)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--spp", type=int, default=8)
+    ap.add_argument("--tree", default=str(Path(__file__).resolve().parent.parent))
     a = ap.parse_args()
+    global oracle, yrt
+    root = Path(a.tree).resolve()
+    for p in (root, root / "yulio-raytracer_amd", root / "tests"):
+        sys.path.insert(0, str(p))
+    import oracle
+    import yrt
     dev = yrt.Device(host=True) if a.host else yrt.Device(0)
     if not a.host:
         dev.set_kernel_timing(True)
@@ -139,7 +141,7 @@ def main():
             r = rows[b]
             med = lambda k: statistics.median(x[k] for x in r)  # noqa: E731
             line = (f"{which:5s} {b:8s} tris {r[0]['tris']:8d} builder {r[0]['builder']} fallback {r[0]['fallback']} "
-                    f"commit {med('commit'):9.2f} ms  bvh {med('bvh'):9.2f} ms (min {min(x['bvh'] for x in r):.2f} "
+                    f"commit {med('commit'):9.2f} ms (min {min(x['commit'] for x in r):.2f} max {max(x['commit'] for x in r):.2f})  bvh {med('bvh'):9.2f} ms (min {min(x['bvh'] for x in r):.2f} "
                     f"max {max(x['bvh'] for x in r):.2f})  kernels {med('kernels'):7.3f} ms  "
                     f"sahCost {r[0]['sahCost']:.3f} nodes {r[0]['nodes']} bvhDepth {r[0]['bvhDepth']}")
             if a.visits:

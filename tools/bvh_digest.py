@@ -1,13 +1,20 @@
 #!/usr/bin/env python3
-"""sha256 of the trees the host builders give, to compare two builds of the library byte for byte.
+"""sha256 of what a scene commit gives on the host, to compare two builds of the library byte for
+byte.
 
 On the host-only device every scene below is committed with "default" (YRT_SBVH unset), "default"
-with YRT_SBVH=1 and "morton" (the host loop); the digest is over the float nodes, the leaf records
-and the quantized nodes (tests/test_refit._exports). One line per scene and setting:
+with YRT_SBVH=1 and "morton" (the host loop); the first digest is over the float nodes, the leaf
+records and the quantized nodes (tests/test_refit._exports). One line per scene and setting:
 
     name  builder  YRT_SBVH  sha256  numNodes  numTriRefs  bvhDepth  (builder, fallback)
+    pools sha256  frame sha256  info sha256
 
-No times, no GPU: two builds that give the same trees print the same text.
+pools: the four yrtDebugTexturePool tables (images, textures, texels, quads); frame: the
+yrtExportFrame blob of a session's scene ("-" for a bare mesh); info: yrtGetSceneInfo without
+buildSeconds. The sessions are C2 to C5 and sphere_motion, so 8-bit textures, a float HDRI image,
+light-bearing primitives and moving geometry are in the set.
+
+No times, no GPU: two builds that commit the same scenes print the same text.
 
     python tools/bvh_digest.py [--tree CHECKOUT] > digest.txt
 
@@ -49,19 +56,28 @@ def main():
     scenes["field_2^17"] = mesh(pos, np.ascontiguousarray(idx[:1 << 17]))
     small = ["-size", "32", "32", "-spp", "1"]
     sessions = {"sphere_motion": ["-c", str(root / "scenes" / "samples" / "sphere_motion.ecs")] + small,
+                "C2": ["-c", str(root / "scenes" / "cornell_box_spheres.ecs")] + small,
                 "C3": ["-i", str(standin.write_xml())] + standin.C3_ARGS + small,
+                "C4": ["-i", str(root / "scenes" / "test_stereo.xml"), "-c", str(root / "scenes" / "test_stereo_view.ecs"),
+                       "-stereo"] + small,
                 "C5": ["-fprCollada", "-i", str(frederick.write_dae()), "-stereo"] + small}
 
     dev = yrt.Device(host=True)
 
-    def line(name, builder, sbvh, scene, exports):
+    def sha(*arrays):
         h = hashlib.sha256()
-        for a in exports:
-            h.update(np.ascontiguousarray(a).tobytes())
+        for a in arrays:
+            h.update(a if isinstance(a, bytes) else np.ascontiguousarray(a).tobytes())
+        return h.hexdigest()
+
+    def line(name, builder, sbvh, scene, exports, frame=None):
         info, bi = dev.scene_info(scene), dev.scene_build_info(scene)
-        print(f"{name:14s} {builder:8s} YRT_SBVH={sbvh or '-'} {h.hexdigest()} nodes {info['numNodes']} "
+        pools = dev.debug_texture_pools(scene)
+        rest = sorted((k, v) for k, v in info.items() if k != "buildSeconds")
+        print(f"{name:14s} {builder:8s} YRT_SBVH={sbvh or '-'} {sha(*exports)} nodes {info['numNodes']} "
               f"refs {info['numTriRefs']} bvhDepth {info['bvhDepth']} builder {bi['builder']} "
-              f"fallback {bi['fallback']}", flush=True)
+              f"fallback {bi['fallback']} pools {sha(*(pools[k] for k in ('images', 'textures', 'texels', 'quads')))} "
+              f"frame {sha(frame) if frame is not None else '-'} info {sha(repr(rest).encode())}", flush=True)
 
     for builder, sbvh in SETTINGS:
         os.environ.pop("YRT_SBVH", None)
@@ -73,7 +89,7 @@ def main():
         for name, args in sessions.items():
             s = yrt.Session(args + ["-builder", builder], device=dev)
             scene = s.info()["scene"]
-            line(name, builder, sbvh, scene, (*dev.export_bvh(scene), dev.export_qbvh(scene)))
+            line(name, builder, sbvh, scene, (*dev.export_bvh(scene), dev.export_qbvh(scene)), s.export_frame())
             s.close()
     dev.close()
 

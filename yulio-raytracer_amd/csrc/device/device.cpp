@@ -49,7 +49,8 @@ HandleRef* Device::ref(YRTHandle h) {
 }
 
 GpuScene& Device::scene_on(SceneObj& S, int dev, bool primary) {
-  static const bool force = getenv("YRT_FORCE_SCENE_REPLICA") != nullptr;
+  // read per call: a process that has rendered before (a test suite) can still switch it on
+  const bool force = getenv("YRT_FORCE_SCENE_REPLICA") != nullptr;
   if (dev == S.gpu->device && (primary || !force)) return *S.gpu;
   auto& r = S.replicas[dev];
   if (!r || r->serial != S.gpu->serial || r->refits != S.gpu->refits) r = replicate_gpu_scene(*S.gpu, dev);

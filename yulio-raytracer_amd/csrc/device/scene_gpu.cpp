@@ -4,6 +4,9 @@
 // BackendSceneFlat ctor (:105-121): geomID = index among primitives that have a shape, in
 // slot order; allLights in slot order; envLights = ambient/HDRI lights. Geometry is the
 // world-space result of Shape::transform, exactly what extract() handed to Embree.
+//
+// build_gpu_scene runs the stages below in turn; a host-only scene skips the two that need a
+// device. The device buffers are listed once, in SceneBuffers (scene_gpu.h).
 #include "scene_gpu.h"
 
 #include <string.h>
@@ -12,12 +15,16 @@
 #include <map>
 
 #include "../common/yrt_tri_record.h"
-#include "bvh_build.h"
 #include "distribution.h"
 
 namespace yrt {
 
-// SceneView pointers of the scene's own device buffers (counts already set in S.view)
+using Prims = std::vector<std::shared_ptr<ScenePrim>>;
+
+template <class V>  // V3 or float4
+static void st3(float* d, const V& v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; }
+
+// SceneView pointers of the scene's own device buffers: the one place that gives them their types
 static void bind_view(GpuScene& S) {
   SceneView& v = S.view;
   v.qnodes = S.qnodes.as<GpuQNode>();
@@ -41,7 +48,7 @@ static void bind_view(GpuScene& S) {
   v.motions = S.motions.as<float4>();
   v.tangents = S.tangents.as<float4>();
   v.triMotion = S.triMotion.as<GpuTriMotion>();
-  v.hdriDist = nullptr;
+  v.hdriDist = nullptr;  // no buffer behind it: the field only keeps the kernel argument's layout
 }
 
 // The device record of a world-space light, without the scene's own indices (image, precomputed
@@ -54,7 +61,6 @@ GpuLight gpu_light_record(const LightInst& L) {
   g.shadowMask = L.shadowMask;
   g.precomputed = -1;
   g.L[0] = L.L.x; g.L[1] = L.L.y; g.L[2] = L.L.z;
-  auto st3 = [](float* d, V3 v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
   st3(g.v0, L.v0); st3(g.v1, L.v1); st3(g.v2, L.v2);
   st3(g.e1, L.e1); st3(g.e2, L.e2); st3(g.Ng, L.Ng);
   auto stA = [](float* d, const A3& a) {
@@ -97,48 +103,68 @@ std::vector<uint32_t> build_tex_quads(const std::vector<GpuImage>& images, const
   return quads;
 }
 
-std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<ScenePrim>>& prims, int stackDepth,
-                                          bool upload, bool morton, hipStream_t stream, bool timing) {
-  auto t0 = std::chrono::steady_clock::now();
-  auto S = std::make_shared<GpuScene>();
-  if (upload) HIP_CHECK(hipGetDevice(&S->device));
+static float4 f4(V3 v) { return make_float4(v.x, v.y, v.z, 0.f); }
+// n vertices of a mesh attribute as the device's float4s; zeros for an attribute the mesh lacks
+static void append_f4(std::vector<float4>& dst, const std::vector<V3>& src, size_t n) {
+  const size_t o = dst.size();
+  dst.resize(o + n, make_float4(0.f, 0.f, 0.f, 0.f));
+  if (!src.empty())
+    for (size_t k = 0; k < n; ++k) dst[o + k] = f4(src[k]);
+}
 
+// The scene bounds: over the vertices the triangles reference, in slot and triangle order
+static void scene_bounds(const Prims& prims, float lo[3], float hi[3]) {
+  for (int k = 0; k < 3; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+  for (const auto& p : prims) {
+    if (!p || !p->shape) continue;
+    const MeshInst& m = *p->shape;
+    for (int v : m.tri) {
+      const float c[3] = {m.pos[v].x, m.pos[v].y, m.pos[v].z};
+      for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], c[k]); hi[k] = std::max(hi[k], c[k]); }
+    }
+  }
+}
+
+// Stage 1, flatten: the host tables of a scene as they are uploaded, filled from the slots without a HIP call.
+// Materials, textures and images are deduplicated by object, media by value.
+struct SceneTables {
   std::vector<float4> positions, normals, motions, tangents;  // tangents: (x, y) per vertex
   std::vector<float2> texcoords;
-  bool anyMotion = false, anyTangent = false;
-  for (const auto& p : prims)
-    if (p && p->shape) {
-      anyMotion |= !p->shape->mot.empty();
-      anyTangent |= !p->shape->tanX.empty() || !p->shape->tanY.empty();
-    }
-  std::vector<float> triVerts1;  // moving scenes: the triangles at the end of the frame time
   std::vector<int4> indices;
-  std::vector<int> triGeom;
-  std::vector<float> triVerts;
+  std::vector<float> triVerts, triVerts1;  // triVerts1 (moving scenes): the triangles at the end of the frame time
   std::vector<uint32_t> triFlags;
+  std::vector<int> triGeom, envLights, primLight;  // primLight: slot -> its light, or -1
   std::vector<GpuGeom> geoms;
   std::vector<GpuMaterial> materials;
   std::vector<GpuTexture> textures;
   std::vector<GpuImage> images;
   // 8-bit images first, float images (HDRI maps) after them: the bilinear footprint records
-  // (texQuads, 4x the bytes) cover only the 8-bit part of the pool
+  // (texQuads, 4x the bytes) cover only the 8-bit part of the pool, texels8Bytes
   std::vector<uint8_t> texels, texelsF;
+  size_t texels8Bytes = 0;
+  // medium table (materials/medium.h): [0] = vacuum; Medium::operator== compares by value, so
+  // media are deduplicated by value and compared by index on the GPU
+  std::vector<float4> media = {make_float4(1.f, 1.f, 1.f, 1.f)};
   std::vector<GpuLight> lights;
-  std::vector<int> envLights;
-  int numEnvZero = 0;
-  int numEnvDir = 0;
+  std::vector<std::shared_ptr<const LightInst>> allLights;
+  std::vector<LightSampleSource> precomputed;
   std::map<const MaterialInst*, int> matIds;
   std::map<const TextureInst*, int> texIds;
   std::map<const ImageObj*, int> imgIds;
+  int numEnvZero = 0, numEnvDir = 0, numTris = 0;
+  bool anyMotion = false, anyTangent = false;
 
-  auto imageId = [&](const std::shared_ptr<ImageObj>& im) -> int {
+  explicit SceneTables(const Prims& prims) { add_lights(prims); add_geoms(prims); place_float_texels(); }
+  void add_lights(const Prims& prims);
+  void add_geoms(const Prims& prims);
+  void place_float_texels();
+
+  int imageId(const std::shared_ptr<ImageObj>& im) {
     auto it = imgIds.find(im.get());
     if (it != imgIds.end()) return it->second;
     GpuImage g;
     memset(&g, 0, sizeof(g));
-    g.width = im->width;
-    g.height = im->height;
-    g.format = im->format;
+    g.width = im->width; g.height = im->height; g.format = im->format;
     std::vector<uint8_t>& pool = im->format == IMG_RGBAF32 ? texelsF : texels;
     size_t off = (pool.size() + 15) & ~size_t(15);
     pool.resize(off);
@@ -146,33 +172,28 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
     pool.insert(pool.end(), im->data.begin(), im->data.end());
     images.push_back(g);
     return imgIds[im.get()] = (int)images.size() - 1;
-  };
-  auto textureId = [&](const std::shared_ptr<const TextureInst>& t) -> int {
+  }
+  int textureId(const std::shared_ptr<const TextureInst>& t) {
     if (!t) return -1;
     auto it = texIds.find(t.get());
     if (it != texIds.end()) return it->second;
     GpuTexture g;
     memset(&g, 0, sizeof(g));
     g.image = imageId(t->image);
-    g.width = images[g.image].width;
-    g.height = images[g.image].height;
-    g.format = images[g.image].format;
-    g.offset = images[g.image].offset;
+    const GpuImage& im = images[g.image];
+    g.width = im.width; g.height = im.height; g.format = im.format; g.offset = im.offset;
     g.filter = t->filter;
     g.invert = t->invert ? 1 : 0;
     textures.push_back(g);
     return texIds[t.get()] = (int)textures.size() - 1;
-  };
-  // medium table (materials/medium.h): [0] = vacuum; Medium::operator== compares by value, so
-  // media are deduplicated by value and compared by index on the GPU
-  std::vector<float4> media = {make_float4(1.f, 1.f, 1.f, 1.f)};
-  auto mediumId = [&](float tr, float tg, float tb, float eta) -> int {
+  }
+  int mediumId(float tr, float tg, float tb, float eta) {
     for (size_t i = 0; i < media.size(); ++i)
       if (media[i].x == tr && media[i].y == tg && media[i].z == tb && media[i].w == eta) return (int)i;
     media.push_back(make_float4(tr, tg, tb, eta));
     return (int)media.size() - 1;
-  };
-  auto materialId = [&](const std::shared_ptr<const MaterialInst>& m) -> int {
+  }
+  int materialId(const std::shared_ptr<const MaterialInst>& m) {
     if (!m) return -1;
     auto it = matIds.find(m.get());
     if (it != matIds.end()) return it->second;
@@ -184,11 +205,34 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
     }
     materials.push_back(g);
     return matIds[m.get()] = (int)materials.size() - 1;
-  };
+  }
+};
 
-  // lights first (allLights in slot order) so geometries can reference their area light
-  std::vector<int> primLight(prims.size(), -1);
-  int numPrecomp = 0;
+// HDRILight::sample (lights/hdrilight.cpp:77-87), evaluated once per sample record
+static LightSampleSource hdri_sample_source(std::shared_ptr<const LightInst> lp) {
+  LightSampleSource src;
+  src.baseSample = 0;  // lightSampleID: first request2D() (pathtraceintegrator.cpp:39)
+  src.sample = [lp](float ux, float uy, float* o) {
+    const int w = lp->image->width, h = lp->image->height;
+    float sx, sy, pdf;
+    dist2d_sample(lp->ycdf, lp->ypdf, lp->xcdf, lp->xpdf, w, h, ux, uy, sx, sy, pdf);
+    const float theta = kPi * sy * rcpf_(float(h));
+    const float phi = kTwoPi * (1.0f - sx * rcpf_(float(w)));
+    const V3 _wi = v3(-sinf(theta) * cosf(phi), cosf(theta), -sinf(theta) * sinf(phi));
+    const V3 wi = xfmVector(lp->l2w, _wi);
+    const float wpdf = pdf * rcpf_(kTwoPi * kPi * sinf(theta));
+    float c[4];
+    lp->image->get(std::max(0, std::min((int)sx, w - 1)), std::max(0, std::min((int)sy, h - 1)), c);
+    o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = wpdf;
+    o[4] = lp->L.x * c[0]; o[5] = lp->L.y * c[1]; o[6] = lp->L.z * c[2];
+    o[7] = INFINITY;
+  };
+  return src;
+}
+
+// allLights in slot order
+void SceneTables::add_lights(const Prims& prims) {
+  primLight.assign(prims.size(), -1);
   for (size_t i = 0; i < prims.size(); ++i) {
     const auto& p = prims[i];
     if (!p || !p->light) continue;
@@ -214,39 +258,31 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
     }
     if (L.type == LIGHT_HDRI) {
       g.image = imageId(L.image);
-      g.hdriW = L.image->width;
-      g.hdriH = L.image->height;
+      g.hdriW = L.image->width; g.hdriH = L.image->height;
     }
     if (L.precompute()) {
-      g.precomputed = numPrecomp++;
-      // HDRILight::sample (lights/hdrilight.cpp:77-87), evaluated once per sample record
-      auto lp = p->light;
-      LightSampleSource src;
-      src.baseSample = 0;  // lightSampleID: first request2D() (pathtraceintegrator.cpp:39)
-      src.sample = [lp](float ux, float uy, float* o) {
-        const int w = lp->image->width, h = lp->image->height;
-        float sx, sy, pdf;
-        dist2d_sample(lp->ycdf, lp->ypdf, lp->xcdf, lp->xpdf, w, h, ux, uy, sx, sy, pdf);
-        const float theta = kPi * sy * rcpf_(float(h));
-        const float phi = kTwoPi * (1.0f - sx * rcpf_(float(w)));
-        const V3 _wi = v3(-sinf(theta) * cosf(phi), cosf(theta), -sinf(theta) * sinf(phi));
-        const V3 wi = xfmVector(lp->l2w, _wi);
-        const float wpdf = pdf * rcpf_(kTwoPi * kPi * sinf(theta));
-        float c[4];
-        lp->image->get(std::max(0, std::min((int)sx, w - 1)), std::max(0, std::min((int)sy, h - 1)), c);
-        o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = wpdf;
-        o[4] = lp->L.x * c[0]; o[5] = lp->L.y * c[1]; o[6] = lp->L.z * c[2];
-        o[7] = INFINITY;
-      };
-      S->precomputed.push_back(src);
+      g.precomputed = (int)precomputed.size();
+      precomputed.push_back(hdri_sample_source(p->light));
     }
     primLight[i] = (int)lights.size();
     lights.push_back(g);
-    S->allLights.push_back(p->light);
+    allLights.push_back(p->light);
   }
+}
 
-  // geometries in slot order (geomID = compacted index)
-  int gidBase = 0;
+// geometries in slot order (geomID = compacted index); after add_lights, so that a geometry can
+// reference its area light
+void SceneTables::add_geoms(const Prims& prims) {
+  for (const auto& p : prims)
+    if (p && p->shape) {
+      anyMotion |= !p->shape->mot.empty();
+      anyTangent |= !p->shape->tanX.empty() || !p->shape->tanY.empty();
+    }
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto push9 = [](std::vector<float>& d, V3 a, V3 b, V3 c) {
+    const float t[9] = {a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z};
+    d.insert(d.end(), t, t + 9);
+  };
   for (size_t i = 0; i < prims.size(); ++i) {
     const auto& p = prims[i];
     if (!p || !p->shape) continue;
@@ -256,290 +292,259 @@ std::shared_ptr<GpuScene> build_gpu_scene(const std::vector<std::shared_ptr<Scen
     g.kind = m.kind;
     g.material = materialId(p->material);
     g.light = primLight[i];
-    g.illumMask = p->illumMask;
-    g.shadowMask = p->shadowMask;
+    g.illumMask = p->illumMask; g.shadowMask = p->shadowMask;
     g.vtxBase = (int)positions.size();
-    g.triBase = gidBase;
+    g.triBase = numTris;
     g.flags = (m.nor.empty() ? 0 : GF_NORMALS) | (m.uv.empty() ? 0 : GF_TEXCOORDS) | (m.cull ? GF_CULL : 0) |
               (m.mot.empty() ? 0 : GF_MOTION) | (m.tanX.empty() ? 0 : GF_TANGENT_X) |
               (m.tanY.empty() ? 0 : GF_TANGENT_Y);
     g.Ng[0] = m.Ng.x; g.Ng[1] = m.Ng.y; g.Ng[2] = m.Ng.z;
     const int geomId = (int)geoms.size();
+    append_f4(positions, m.pos, m.pos.size());
+    append_f4(normals, m.nor, m.pos.size());
+    if (anyMotion) append_f4(motions, m.mot, m.pos.size());
     for (size_t k = 0; k < m.pos.size(); ++k) {
-      positions.push_back(make_float4(m.pos[k].x, m.pos[k].y, m.pos[k].z, 0.f));
-      if (!m.nor.empty()) normals.push_back(make_float4(m.nor[k].x, m.nor[k].y, m.nor[k].z, 0.f));
-      else normals.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
-      if (!m.uv.empty()) texcoords.push_back(make_float2(m.uv[2 * k], m.uv[2 * k + 1]));
-      else texcoords.push_back(make_float2(0.f, 0.f));
-      if (anyMotion)
-        motions.push_back(m.mot.empty() ? make_float4(0.f, 0.f, 0.f, 0.f)
-                                        : make_float4(m.mot[k].x, m.mot[k].y, m.mot[k].z, 0.f));
+      texcoords.push_back(m.uv.empty() ? make_float2(0.f, 0.f) : make_float2(m.uv[2 * k], m.uv[2 * k + 1]));
       if (anyTangent) {
-        tangents.push_back(m.tanX.empty() ? make_float4(0.f, 0.f, 0.f, 0.f)
-                                          : make_float4(m.tanX[k].x, m.tanX[k].y, m.tanX[k].z, 0.f));
-        tangents.push_back(m.tanY.empty() ? make_float4(0.f, 0.f, 0.f, 0.f)
-                                          : make_float4(m.tanY[k].x, m.tanY[k].y, m.tanY[k].z, 0.f));
+        tangents.push_back(m.tanX.empty() ? zero : f4(m.tanX[k]));
+        tangents.push_back(m.tanY.empty() ? zero : f4(m.tanY[k]));
       }
     }
+    auto mot = [&](int v) { return m.mot.empty() ? v3s(0.f) : m.mot[v]; };
     const int nt = (int)(m.tri.size() / 3);
     for (int t = 0; t < nt; ++t) {
       const int a = m.tri[3 * t], b = m.tri[3 * t + 1], c = m.tri[3 * t + 2];
       indices.push_back(make_int4(g.vtxBase + a, g.vtxBase + b, g.vtxBase + c, geomId));
       triGeom.push_back(geomId);
-      const V3 va = m.pos[a], vb = m.pos[b], vc = m.pos[c];
-      const float tv[9] = {va.x, va.y, va.z, vb.x, vb.y, vb.z, vc.x, vc.y, vc.z};
-      triVerts.insert(triVerts.end(), tv, tv + 9);
-      if (anyMotion) {  // p + m: the vertices at time 1 (trianglemesh_full.cpp:152-166)
-        const V3 z = v3s(0.f);
-        const V3 ma = m.mot.empty() ? z : m.mot[a], mb = m.mot.empty() ? z : m.mot[b], mc = m.mot.empty() ? z : m.mot[c];
-        const V3 qa = va + ma, qb = vb + mb, qc = vc + mc;
-        const float tv1[9] = {qa.x, qa.y, qa.z, qb.x, qb.y, qb.z, qc.x, qc.y, qc.z};
-        triVerts1.insert(triVerts1.end(), tv1, tv1 + 9);
-      }
+      push9(triVerts, m.pos[a], m.pos[b], m.pos[c]);
+      // p + m: the vertices at time 1 (trianglemesh_full.cpp:152-166)
+      if (anyMotion) push9(triVerts1, m.pos[a] + mot(a), m.pos[b] + mot(b), m.pos[c] + mot(c));
       triFlags.push_back(m.cull ? 1u : 0u);
     }
-    gidBase += nt;
+    numTris += nt;
     geoms.push_back(g);
   }
-  if (gidBase >= (1 << 26)) throw std::runtime_error("scene exceeds 2^26 triangles (stack entry packing)");
+  if (numTris >= (1 << 26)) throw std::runtime_error("scene exceeds 2^26 triangles (stack entry packing)");
+}
 
+// place the float images after the 8-bit ones; image and texture records get final offsets
+void SceneTables::place_float_texels() {
+  texels8Bytes = (texels.size() + 15) & ~size_t(15);
+  texels.resize(texels8Bytes);
+  texels.insert(texels.end(), texelsF.begin(), texelsF.end());
+  for (GpuImage& g : images)
+    if (g.format == IMG_RGBAF32) g.offset += (int64_t)texels8Bytes;
+  for (GpuTexture& t : textures) t.offset = images[t.image].offset;
+}
+
+struct SceneBvh {
   BvhResult bvh;
-  {
-    const auto tb = std::chrono::steady_clock::now();
-    const std::vector<float>* v1 = anyMotion ? &triVerts1 : nullptr;
-    BuildInfo& bi = S->buildInfo;
-    S->mortonAsked = morton;
-    if (morton) {
-      bi.builder = upload ? BUILDER_MORTON_GPU : BUILDER_MORTON_HOST;
-      bi.fallback = upload ? build_bvh_morton_gpu(triVerts, triFlags, stackDepth, bvh, v1, stream, timing, &bi.msKernels)
-                           : build_bvh_morton_host(triVerts, triFlags, stackDepth, bvh, v1);
-    }
-    if (!morton || bi.fallback != FALLBACK_NONE) {
-      bi.builder = BUILDER_SAH;
-      bi.msKernels = 0;
-      build_bvh(triVerts, triFlags, stackDepth, bvh, v1);
-    }
-    bi.msBuild = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
-    bi.sahCost = bvh_sah_cost(bvh.nodes);
+  std::vector<GpuQNode> qnodes;  // the any-hit kernels' 64-B nodes (common/yrt_qnode.h), node for node
+};
+
+// Stage 2, BVH: runs the builder asked for (the host SAH builder where "morton" declines), fills S.buildInfo
+static SceneBvh build_scene_bvh(GpuScene& S, const SceneTables& T, int stackDepth, bool upload, bool morton,
+                                hipStream_t stream, bool timing) {
+  SceneBvh B;
+  BvhResult& bvh = B.bvh;
+  const auto tb = std::chrono::steady_clock::now();
+  const std::vector<float>* v1 = T.anyMotion ? &T.triVerts1 : nullptr;
+  BuildInfo& bi = S.buildInfo;
+  S.mortonAsked = morton;
+  if (morton) {
+    bi.builder = upload ? BUILDER_MORTON_GPU : BUILDER_MORTON_HOST;
+    bi.fallback = upload ? build_bvh_morton_gpu(T.triVerts, T.triFlags, stackDepth, bvh, v1, stream, timing, &bi.msKernels)
+                         : build_bvh_morton_host(T.triVerts, T.triFlags, stackDepth, bvh, v1);
   }
+  if (!morton || bi.fallback != FALLBACK_NONE) {
+    bi.builder = BUILDER_SAH;
+    bi.msKernels = 0;
+    build_bvh(T.triVerts, T.triFlags, stackDepth, bvh, v1);
+  }
+  bi.msBuild = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
+  bi.sahCost = bvh_sah_cost(bvh.nodes);
   // each leaf record carries its triangle's geometry id (GpuTri::e2[3]): part of the record's
   // layout as exported; the kernels take the id from the shading record (GpuTriShade)
-  for (size_t i = 0; i < bvh.tris.size(); ++i) memcpy(&bvh.tris[i].e2[3], &triGeom[bvh.order[i]], 4);
-  // the any-hit kernels' 64-B nodes (common/yrt_qnode.h), node for node
-  std::vector<GpuQNode> qnodes(bvh.nodes.size());
-  for (size_t i = 0; i < bvh.nodes.size(); ++i) yrt_quantize_node(bvh.nodes[i], qnodes[i]);
-  S->hasMotion = anyMotion;
-  S->bvhDepth = bvh.maxDepth;
-  S->numTris = gidBase;
-  S->numGeoms = (int)geoms.size();
-  for (int k = 0; k < 3; ++k) { S->bboxLo[k] = INFINITY; S->bboxHi[k] = -INFINITY; }
-  for (size_t i = 0; i < triVerts.size(); i += 3)
+  for (size_t i = 0; i < bvh.tris.size(); ++i) memcpy(&bvh.tris[i].e2[3], &T.triGeom[bvh.order[i]], 4);
+  B.qnodes.resize(bvh.nodes.size());
+  for (size_t i = 0; i < bvh.nodes.size(); ++i) yrt_quantize_node(bvh.nodes[i], B.qnodes[i]);
+  S.bvhDepth = bvh.maxDepth;
+  return B;
+}
+
+// Stage 3, derived records. Per leaf slot: the moving triangle's other vertices and the vertex motions
+static std::vector<GpuTriMotion> tri_motion_records(const SceneTables& T, const std::vector<int>& order) {
+  std::vector<GpuTriMotion> tm(order.size());
+  for (size_t i = 0; i < order.size(); ++i) {
+    const int4 ix = T.indices[order[i]];
+    GpuTriMotion& r = tm[i];
+    memset(&r, 0, sizeof(r));
+    st3(r.p1, T.positions[ix.y]); st3(r.p2, T.positions[ix.z]);
+    st3(r.m0, T.motions[ix.x]); st3(r.m1, T.motions[ix.y]); st3(r.m2, T.motions[ix.z]);
+  }
+  return tm;
+}
+
+// Per triangle: what k_shade reads of its three vertices (common/yrt_tri_record.h)
+static std::vector<GpuTriShade> tri_shade_records(const SceneTables& T) {
+  std::vector<GpuTriShade> ts(T.indices.size());
+  for (size_t t = 0; t < T.indices.size(); ++t) {
+    const int4 ix = T.indices[t];
+    const int v[3] = {ix.x, ix.y, ix.z};
+    float p[3][3], n[3][3], st[3][2];
     for (int k = 0; k < 3; ++k) {
-      S->bboxLo[k] = std::min(S->bboxLo[k], triVerts[i + k]);
-      S->bboxHi[k] = std::max(S->bboxHi[k], triVerts[i + k]);
+      st3(p[k], T.positions[v[k]]); st3(n[k], T.normals[v[k]]);
+      st[k][0] = T.texcoords[v[k]].x; st[k][1] = T.texcoords[v[k]].y;
     }
+    yrt_tri_shade_fill(ts[t], p[0], p[1], p[2], n[0], n[1], n[2], st[0], st[1], st[2], ix.w);
+  }
+  return ts;
+}
 
-  {
-    // place the float images after the 8-bit ones; image and texture records get final offsets
-    const size_t base = (texels.size() + 15) & ~size_t(15);
-    S->texels8Bytes = base;
-    texels.resize(base);
-    texels.insert(texels.end(), texelsF.begin(), texelsF.end());
-    for (GpuImage& g : images)
-      if (g.format == IMG_RGBAF32) g.offset += (int64_t)base;
-    for (GpuTexture& t : textures) t.offset = images[t.image].offset;
-  }
-  S->texelsBytes = texels.size();
-  S->hMaterials = materials;
-  S->hTextures = textures;
-  S->hImages = images;
-  S->hMedia = media;
-  if (!upload) {
-    S->hTexels = std::move(texels);  // a host-only scene's pool (yrtDebugTexturePool)
-    S->hNodes = std::move(bvh.nodes);
-    S->hQNodes = std::move(qnodes);
-    S->hTris = std::move(bvh.tris);
-    S->hGeoms = geoms;
-    S->hTriGeom = triGeom;
-    S->view.numLights = (int)lights.size();
-    S->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return S;
-  }
-  for (const GpuMaterial& m : materials) S->materialMask |= 1u << m.type;
-  for (const GpuLight& l : lights) S->materialMask |= 1u << (16 + l.type);  // light_bit (kernels/yrt_shade.h)
-  S->nodes.upload(bvh.nodes);
-  S->qnodes.upload(qnodes);
-  S->tris.upload(bvh.tris);
-  S->triGeom.upload(triGeom);
-  S->indices.upload(indices);
-  S->positions.upload(positions);
-  if (anyMotion) {
-    S->motions.upload(motions);
-    // per leaf slot: the moving triangle's other vertices and the vertex motions
-    std::vector<GpuTriMotion> tm(bvh.tris.size());
-    for (size_t i = 0; i < bvh.tris.size(); ++i) {
-      const int gid = bvh.order[i];
-      const int4 ix = indices[gid];
-      const int vtx[3] = {ix.x, ix.y, ix.z};
-      GpuTriMotion& r = tm[i];
-      memset(&r, 0, sizeof(r));
-      const float4 p1 = positions[vtx[1]], p2 = positions[vtx[2]];
-      r.p1[0] = p1.x; r.p1[1] = p1.y; r.p1[2] = p1.z;
-      r.p2[0] = p2.x; r.p2[1] = p2.y; r.p2[2] = p2.z;
-      float* ms[3] = {r.m0, r.m1, r.m2};
-      for (int k = 0; k < 3; ++k) {
-        const float4 mv = motions[vtx[k]];
-        ms[k][0] = mv.x; ms[k][1] = mv.y; ms[k][2] = mv.z;
-      }
+// Per geometry: the geometry with its material and the material's first texture
+static std::vector<GpuGeomRec> geom_records(const SceneTables& T) {
+  std::vector<GpuGeomRec> recs(T.geoms.size());
+  for (size_t i = 0; i < T.geoms.size(); ++i) {
+    GpuGeomRec& r = recs[i];
+    memset(&r, 0, sizeof(r));
+    r.g = T.geoms[i];
+    if (r.g.material >= 0) {
+      r.m = T.materials[r.g.material];
+      if (r.m.tex[0] >= 0) r.t0 = T.textures[r.m.tex[0]];
     }
-    S->triMotion.upload(tm);
   }
-  if (anyTangent) S->tangents.upload(tangents);
-  S->normals.upload(normals);
-  S->texcoords.upload(texcoords);
-  S->geoms.upload(geoms);
-  {
-    std::vector<GpuTriShade> ts(indices.size());
-    for (size_t t = 0; t < indices.size(); ++t) {
-      const int4 ix = indices[t];
-      const int v[3] = {ix.x, ix.y, ix.z};
-      float p[3][3], n[3][3], st[3][2];
-      for (int k = 0; k < 3; ++k) {
-        const float4 pk = positions[v[k]], nk = normals[v[k]];
-        p[k][0] = pk.x; p[k][1] = pk.y; p[k][2] = pk.z;
-        n[k][0] = nk.x; n[k][1] = nk.y; n[k][2] = nk.z;
-        st[k][0] = texcoords[v[k]].x; st[k][1] = texcoords[v[k]].y;
-      }
-      yrt_tri_shade_fill(ts[t], p[0], p[1], p[2], n[0], n[1], n[2], st[0], st[1], st[2], ix.w);
-    }
-    S->triShade.upload(ts);
-  }
-  {
-    std::vector<GpuGeomRec> recs(geoms.size());
-    for (size_t i = 0; i < geoms.size(); ++i) {
-      GpuGeomRec& r = recs[i];
-      memset(&r, 0, sizeof(r));
-      r.g = geoms[i];
-      if (r.g.material >= 0) {
-        r.m = materials[r.g.material];
-        if (r.m.tex[0] >= 0) r.t0 = textures[r.m.tex[0]];
-      }
-    }
-    S->geomRecs.upload(recs);
-  }
-  S->materials.upload(materials);
-  S->textures.upload(textures);
-  S->images.upload(images);
-  S->texels.upload(texels);
-  S->texQuads.upload(build_tex_quads(images, texels, S->texels8Bytes));
-  S->lights.upload(lights);
-  S->hLights = lights;
-  S->hEnvLights = envLights;
-  S->envLights.upload(envLights);
-  S->media.upload(media);
+  return recs;
+}
 
-  S->view.numLights = (int)lights.size();
-  S->view.numEnvLights = (int)envLights.size();
-  S->view.numEnvZero = numEnvZero;
-  S->view.numEnvDir = numEnvDir;
-  S->view.numNodes = (int)bvh.nodes.size();
-  S->view.numTris = gidBase;
-  bind_view(*S);
-
-  // refit support: slot -> geometry, gid -> leaf position, nodes grouped by depth
-  S->slotsCommitted = prims;
-  S->slotGeom.assign(prims.size(), -1);
-  {
-    int gcount = 0;
-    for (size_t i = 0; i < prims.size(); ++i)
-      if (prims[i] && prims[i]->shape) S->slotGeom[i] = gcount++;
-    // gid -> leaf slots (CSR: gidBase + 1 offsets, then the slots; spatial splits can put a
-    // triangle in several leaves)
-    std::vector<int> leafOf(gidBase + 1 + bvh.order.size(), 0);
-    for (int g : bvh.order) leafOf[g + 1]++;
-    for (int g = 0; g < gidBase; ++g) leafOf[g + 1] += leafOf[g];
-    std::vector<int> fill(leafOf.begin(), leafOf.begin() + gidBase);
-    for (size_t i = 0; i < bvh.order.size(); ++i) leafOf[gidBase + 1 + fill[bvh.order[i]]++] = (int)i;
-    S->triLeaf.upload(leafOf);
-    std::vector<std::vector<int>> levels;
-    std::vector<std::pair<int, int>> work = {{0, 0}};
-    for (size_t w = 0; w < work.size(); ++w) {
-      const int ni = work[w].first, d = work[w].second;
-      if ((int)levels.size() <= d) levels.resize(d + 1);
-      levels[d].push_back(ni);
-      for (int k = 0; k < 4; ++k) {
-        const int c = bvh.nodes[ni].child[k];
-        if (c != -1 && (c & 31) == 0) work.push_back({c >> 5, d + 1});
-      }
-    }
-    std::vector<int> flat;
-    S->levelStart.clear();
-    for (auto& l : levels) {
-      S->levelStart.push_back((int)flat.size());
-      flat.insert(flat.end(), l.begin(), l.end());
-    }
-    S->levelStart.push_back((int)flat.size());
-    S->levelNodes.upload(flat);
+// Stage 4, upload and view: in this order, which is also the order of the allocations
+static void upload_scene(GpuScene& S, const SceneTables& T, const SceneBvh& B) {
+  for (const GpuMaterial& m : T.materials) S.materialMask |= 1u << m.type;
+  for (const GpuLight& l : T.lights) S.materialMask |= 1u << (16 + l.type);  // light_bit (kernels/yrt_shade.h)
+  S.nodes.upload(B.bvh.nodes);
+  S.qnodes.upload(B.qnodes);
+  S.tris.upload(B.bvh.tris);
+  S.triGeom.upload(T.triGeom);
+  S.indices.upload(T.indices);
+  S.positions.upload(T.positions);
+  if (T.anyMotion) {
+    S.motions.upload(T.motions);
+    S.triMotion.upload(tri_motion_records(T, B.bvh.order));
   }
+  if (T.anyTangent) S.tangents.upload(T.tangents);
+  S.normals.upload(T.normals);
+  S.texcoords.upload(T.texcoords);
+  S.geoms.upload(T.geoms);
+  S.triShade.upload(tri_shade_records(T));
+  S.geomRecs.upload(geom_records(T));
+  S.materials.upload(T.materials);
+  S.textures.upload(T.textures);
+  S.images.upload(T.images);
+  S.texels.upload(T.texels);
+  S.texQuads.upload(build_tex_quads(T.images, T.texels, T.texels8Bytes));
+  S.lights.upload(T.lights);
+  S.envLights.upload(T.envLights);
+  S.media.upload(T.media);
+  bind_view(S);
+}
 
-  S->hNodes = std::move(bvh.nodes);
-  S->hQNodes = std::move(qnodes);
-  S->hTris = std::move(bvh.tris);
-  S->hGeoms = geoms;
-  S->hTriGeom = triGeom;
+// Stage 5, refit tables: slot -> geometry, gid -> leaf position, nodes grouped by depth (refit_gpu_scene)
+static void build_refit_tables(GpuScene& S, const Prims& prims, const BvhResult& bvh, int numTris) {
+  S.slotsCommitted = prims;
+  S.slotGeom.assign(prims.size(), -1);
+  int gcount = 0;
+  for (size_t i = 0; i < prims.size(); ++i)
+    if (prims[i] && prims[i]->shape) S.slotGeom[i] = gcount++;
+  // gid -> leaf slots (CSR: numTris + 1 offsets, then the slots; spatial splits can put a
+  // triangle in several leaves)
+  std::vector<int> leafOf(numTris + 1 + bvh.order.size(), 0);
+  for (int g : bvh.order) leafOf[g + 1]++;
+  for (int g = 0; g < numTris; ++g) leafOf[g + 1] += leafOf[g];
+  std::vector<int> fill(leafOf.begin(), leafOf.begin() + numTris);
+  for (size_t i = 0; i < bvh.order.size(); ++i) leafOf[numTris + 1 + fill[bvh.order[i]]++] = (int)i;
+  S.triLeaf.upload(leafOf);
+  std::vector<std::vector<int>> levels;
+  std::vector<std::pair<int, int>> work = {{0, 0}};
+  for (size_t w = 0; w < work.size(); ++w) {
+    const int ni = work[w].first, d = work[w].second;
+    if ((int)levels.size() <= d) levels.resize(d + 1);
+    levels[d].push_back(ni);
+    for (int k = 0; k < 4; ++k) {
+      const int c = bvh.nodes[ni].child[k];
+      if (c != -1 && (c & 31) == 0) work.push_back({c >> 5, d + 1});
+    }
+  }
+  std::vector<int> flat;
+  S.levelStart.clear();
+  for (auto& l : levels) {
+    S.levelStart.push_back((int)flat.size());
+    flat.insert(flat.end(), l.begin(), l.end());
+  }
+  S.levelStart.push_back((int)flat.size());
+  S.levelNodes.upload(flat);
+}
+
+// Stage 6, counts and host mirrors: takes the tables over. The texel pool stays only with a host-only
+// scene, which has no device copy of it (yrtDebugTexturePool).
+static void set_mirrors(GpuScene& S, SceneTables&& T, SceneBvh&& B, bool upload) {
+  S.hasMotion = T.anyMotion;
+  S.numTris = S.view.numTris = T.numTris;
+  S.numGeoms = (int)T.geoms.size();
+  S.texels8Bytes = T.texels8Bytes; S.texelsBytes = T.texels.size();
+  S.view.numNodes = (int)B.bvh.nodes.size();
+  S.view.numLights = (int)T.lights.size(); S.view.numEnvLights = (int)T.envLights.size();
+  S.view.numEnvZero = T.numEnvZero; S.view.numEnvDir = T.numEnvDir;
+  S.hMaterials = std::move(T.materials); S.hTextures = std::move(T.textures); S.hImages = std::move(T.images);
+  S.hMedia = std::move(T.media);
+  if (!upload) S.hTexels = std::move(T.texels);
+  S.hNodes = std::move(B.bvh.nodes); S.hQNodes = std::move(B.qnodes); S.hTris = std::move(B.bvh.tris);
+  S.hGeoms = std::move(T.geoms); S.hTriGeom = std::move(T.triGeom);
+  S.allLights = std::move(T.allLights); S.hLights = std::move(T.lights); S.hEnvLights = std::move(T.envLights);
+  S.precomputed = std::move(T.precomputed);
+}
+
+std::shared_ptr<GpuScene> build_gpu_scene(const Prims& prims, int stackDepth, bool upload, bool morton,
+                                          hipStream_t stream, bool timing) {
+  auto t0 = std::chrono::steady_clock::now();
+  auto S = std::make_shared<GpuScene>();
+  if (upload) HIP_CHECK(hipGetDevice(&S->device));
+  SceneTables T(prims);
+  SceneBvh B = build_scene_bvh(*S, T, stackDepth, upload, morton, stream, timing);
+  scene_bounds(prims, S->bboxLo, S->bboxHi);
+  if (upload) {
+    upload_scene(*S, T, B);
+    build_refit_tables(*S, prims, B.bvh, T.numTris);
+  }
+  set_mirrors(*S, std::move(T), std::move(B), upload);
   S->buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return S;
 }
 
+// The scalar fields a replica shares with its source, then the buffers of SceneBuffers::all; the
+// host mirrors other than the light tables stay with the source.
 std::shared_ptr<GpuScene> replicate_gpu_scene(const GpuScene& src, int device) {
   HIP_CHECK(hipSetDevice(device));
   auto R = std::make_shared<GpuScene>();
   R->device = device;
   R->serial = src.serial;  // same committed scene: the sample-table caches may key on it
-  auto copy = [&](DevBuf& dst, const DevBuf& from) {
-    if (!from.p) return;
-    dst.alloc(from.bytes);
-    HIP_CHECK(hipMemcpyPeer(dst.p, device, from.p, src.device, from.bytes));
-  };
-  copy(R->nodes, src.nodes);
-  copy(R->qnodes, src.qnodes);
-  copy(R->tris, src.tris);
-  copy(R->triGeom, src.triGeom);
-  copy(R->indices, src.indices);
-  copy(R->positions, src.positions);
-  copy(R->normals, src.normals);
-  copy(R->texcoords, src.texcoords);
-  copy(R->geoms, src.geoms);
-  copy(R->geomRecs, src.geomRecs);
-  copy(R->triShade, src.triShade);
-  copy(R->materials, src.materials);
-  copy(R->textures, src.textures);
-  copy(R->images, src.images);
-  copy(R->texels, src.texels);
-  copy(R->texQuads, src.texQuads);
-  copy(R->lights, src.lights);
-  copy(R->envLights, src.envLights);
-  copy(R->media, src.media);
-  copy(R->motions, src.motions);
-  copy(R->triMotion, src.triMotion);
-  copy(R->tangents, src.tangents);
+  for (DevBuf SceneBuffers::*b : SceneBuffers::all) {
+    const DevBuf& from = src.*b;
+    if (!from.p) continue;
+    ((*R).*b).alloc(from.bytes);
+    HIP_CHECK(hipMemcpyPeer(((*R).*b).p, device, from.p, src.device, from.bytes));
+  }
   R->hasMotion = src.hasMotion;
   R->view = src.view;
   bind_view(*R);
   R->materialMask = src.materialMask;
   R->precomputed = src.precomputed;
-  R->hLights = src.hLights;
-  R->hEnvLights = src.hEnvLights;
-  R->numTris = src.numTris;
-  R->numGeoms = src.numGeoms;
-  R->bvhDepth = src.bvhDepth;
+  R->hLights = src.hLights; R->hEnvLights = src.hEnvLights;
+  R->numTris = src.numTris; R->numGeoms = src.numGeoms; R->bvhDepth = src.bvhDepth;
   R->refits = src.refits;
-  R->texels8Bytes = src.texels8Bytes;
-  R->texelsBytes = src.texelsBytes;
+  R->texels8Bytes = src.texels8Bytes; R->texelsBytes = src.texelsBytes;
   return R;
 }
 
-bool refit_gpu_scene(GpuScene& S, const std::vector<std::shared_ptr<ScenePrim>>& prims, hipStream_t stream) {
+bool refit_gpu_scene(GpuScene& S, const Prims& prims, hipStream_t stream) {
   // moving geometry: boxes span the frame time and leaf records carry motion (rebuild instead)
   if (!S.nodes.p || prims.size() != S.slotsCommitted.size() || S.hNodes.empty() || S.hasMotion) return false;
   std::vector<size_t> moved;
@@ -561,9 +566,7 @@ bool refit_gpu_scene(GpuScene& S, const std::vector<std::shared_ptr<ScenePrim>>&
       return x.size() == y.size() && (x.empty() || !memcmp(x.data(), y.data(), x.size() * sizeof(V3)));
     };
     if (!same_v3(a.tanX, b.tanX) || !same_v3(a.tanY, b.tanY)) return false;
-    const bool same = !memcmp(a.pos.data(), b.pos.data(), a.pos.size() * sizeof(V3)) &&
-                      (a.nor.empty() || !memcmp(a.nor.data(), b.nor.data(), a.nor.size() * sizeof(V3)));
-    if (!same) moved.push_back(i);
+    if (!same_v3(a.pos, b.pos) || !same_v3(a.nor, b.nor)) moved.push_back(i);
   }
   S.slotsCommitted = prims;  // unchanged geometry: adopt the new slot objects (export)
   if (moved.empty()) return true;
@@ -571,11 +574,9 @@ bool refit_gpu_scene(GpuScene& S, const std::vector<std::shared_ptr<ScenePrim>>&
   for (size_t i : moved) {
     const MeshInst& m = *prims[i]->shape;
     const GpuGeom& g = S.hGeoms[S.slotGeom[i]];
-    std::vector<float4> pos(m.pos.size()), nor(m.pos.size());
-    for (size_t k = 0; k < m.pos.size(); ++k) {
-      pos[k] = make_float4(m.pos[k].x, m.pos[k].y, m.pos[k].z, 0.f);
-      nor[k] = m.nor.empty() ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(m.nor[k].x, m.nor[k].y, m.nor[k].z, 0.f);
-    }
+    std::vector<float4> pos, nor;
+    append_f4(pos, m.pos, m.pos.size());
+    append_f4(nor, m.nor, m.pos.size());
     HIP_CHECK(hipMemcpyAsync(S.positions.as<float4>() + g.vtxBase, pos.data(), pos.size() * sizeof(float4),
                              hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(S.normals.as<float4>() + g.vtxBase, nor.data(), nor.size() * sizeof(float4),
@@ -590,19 +591,7 @@ bool refit_gpu_scene(GpuScene& S, const std::vector<std::shared_ptr<ScenePrim>>&
     launch_refit_nodes(S.nodes.as<GpuNode>(), S.tris.as<GpuTri>(), S.indices.as<int4>(), S.positions.as<float4>(),
                        S.levelNodes.as<int>() + S.levelStart[d], S.levelStart[d + 1] - S.levelStart[d], stream);
   launch_quantize_nodes(S.nodes.as<GpuNode>(), S.qnodes.as<GpuQNode>(), (int)S.hNodes.size(), stream);
-  // the scene bounds, as the build takes them: over the vertices the triangles reference
-  for (int k = 0; k < 3; ++k) { S.bboxLo[k] = INFINITY; S.bboxHi[k] = -INFINITY; }
-  for (const auto& p : prims) {
-    if (!p || !p->shape) continue;
-    const MeshInst& m = *p->shape;
-    for (int v : m.tri) {
-      const float c[3] = {m.pos[v].x, m.pos[v].y, m.pos[v].z};
-      for (int k = 0; k < 3; ++k) {
-        S.bboxLo[k] = std::min(S.bboxLo[k], c[k]);
-        S.bboxHi[k] = std::max(S.bboxHi[k], c[k]);
-      }
-    }
-  }
+  scene_bounds(prims, S.bboxLo, S.bboxHi);  // as the build takes them
   HIP_CHECK(hipStreamSynchronize(stream));
   S.hostBvhStale = true;
   S.refits++;

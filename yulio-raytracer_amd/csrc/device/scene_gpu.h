@@ -1,66 +1,47 @@
-// scene_gpu.h — a committed scene flattened into HBM (layout: common/yrt_gpu_types.h).
+// scene_gpu.h — a committed scene flattened into HBM (layout: common/yrt_gpu_types.h): its device
+// buffers (SceneBuffers, listed once), host mirrors and refit tables; build, peer copy, refit.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include <memory>
-#include <stdexcept>
-#include <string>
 #include <atomic>
+#include <iterator>
+#include <memory>
 #include <vector>
 
 #include "../kernels/yrt_kernels.h"
 #include "bvh_build.h"
+#include "dev_buf.h"
 #include "objects.h"
 #include "sampler.h"
 
 namespace yrt {
 
-#define HIP_CHECK(x)                                                                              \
-  do {                                                                                            \
-    hipError_t _e = (x);                                                                          \
-    if (_e != hipSuccess)                                                                         \
-      throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(_e) + " at " #x);    \
-  } while (0)
-
-// RAII device allocation
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() {}
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  void alloc(size_t n) {
-    if (n <= bytes && p) return;
-    release();
-    if (n == 0) n = 16;
-    HIP_CHECK(hipMalloc(&p, n));
-    bytes = n;
-  }
-  template <class T>
-  void upload(const std::vector<T>& v) {
-    alloc(v.size() * sizeof(T));
-    if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
+// The device buffers of a scene that its replica on another GPU needs too: what SceneView points
+// at, and the float nodes. `all` is the one list of them: replicate_gpu_scene copies what it names,
+// in that order, and bind_view (scene_gpu.cpp) gives the buffers their types. A buffer declared
+// here without an entry in `all` fails the static_assert below.
+struct SceneBuffers {
+  DevBuf nodes, qnodes, tris, triGeom, indices, positions, normals, texcoords, geoms, materials, textures, images, texels, texQuads,
+      lights, envLights, media, geomRecs, motions, tangents, triMotion, triShade;
+  static constexpr DevBuf SceneBuffers::*all[] = {
+      &SceneBuffers::nodes,     &SceneBuffers::qnodes,    &SceneBuffers::tris,     &SceneBuffers::triGeom,
+      &SceneBuffers::indices,   &SceneBuffers::positions, &SceneBuffers::normals,  &SceneBuffers::texcoords,
+      &SceneBuffers::geoms,     &SceneBuffers::geomRecs,  &SceneBuffers::triShade, &SceneBuffers::materials,
+      &SceneBuffers::textures,  &SceneBuffers::images,    &SceneBuffers::texels,   &SceneBuffers::texQuads,
+      &SceneBuffers::lights,    &SceneBuffers::envLights, &SceneBuffers::media,    &SceneBuffers::motions,
+      &SceneBuffers::triMotion, &SceneBuffers::tangents};
 };
+static_assert(sizeof(SceneBuffers) == std::size(SceneBuffers::all) * sizeof(DevBuf),
+              "every DevBuf of SceneBuffers needs an entry in SceneBuffers::all (a replica would miss it)");
 
-struct GpuScene {
+struct GpuScene : SceneBuffers {
   int device = 0;
   uint64_t serial = next_serial();  // identifies the committed scene in caches (addresses get reused)
   static uint64_t next_serial() {
     static std::atomic<uint64_t> n{1};
     return n++;
   }
-  DevBuf nodes, qnodes, tris, triGeom, indices, positions, normals, texcoords, geoms, materials, textures, images, texels, texQuads,
-      lights, envLights, hdriDist, media, geomRecs, motions, tangents, triMotion, triShade;
   bool hasMotion = false;  // moving geometry: time-aware trace kernels, no refit
   SceneView view{};
   unsigned materialMask = 0;  // bit MAT_x per material type, bit 16+LIGHT_x per light type used (shade kernel variant)
@@ -88,6 +69,8 @@ struct GpuScene {
   std::vector<std::shared_ptr<ScenePrim>> slotsCommitted;
   std::vector<int> slotGeom;
   std::vector<int> levelStart;  // nodes of depth d: levelNodes[levelStart[d] .. levelStart[d+1])
+  // the refit kernels' tables: with the primary only, outside SceneBuffers::all on purpose (a
+  // refit runs on the primary, whose replicas are then copied again)
   DevBuf triLeaf, levelNodes;
   bool hostBvhStale = false;    // hNodes/hTris lag a device refit until sync_host_bvh
   int refits = 0;               // refit commits since the build (stats)
