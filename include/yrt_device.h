@@ -121,7 +121,10 @@ YRT_API int yrtRenderFrame(YRTDevice dev, YRTHandle renderer, YRTHandle camera, 
  * dealt over shards and GPUs as a whole, with one gather per job. This is the loop of the
  * stereo-cube drivers over the 12 faces of a view (renderer.cpp:543-737, 742-878) when no
  * primitive changes between the faces. accumulate != 0 is accepted for numFrames == 1 only (a
- * job keeps one sampler iteration and no per-frame accumulation state across calls). */
+ * job keeps one sampler iteration and no per-frame accumulation state across calls). For the
+ * same reason yrtRenderFrame(..., accumulate = 1) into a framebuffer whose last frame came from a
+ * job of several frames fails with an error, until a frame with accumulate = 0 has been rendered
+ * into it: the accumulation buffer belongs to the framebuffer, and such a job does not fill it. */
 YRT_API int yrtRenderFrames(YRTDevice dev, YRTHandle renderer, const YRTHandle* cameras, int numFrames,
                             YRTHandle scene, YRTHandle tonemapper, const YRTHandle* framebuffers, int accumulate);
 YRT_API void* yrtMapFrameBuffer(YRTDevice dev, YRTHandle framebuffer, int bufID);

@@ -48,6 +48,8 @@ _sig("oracle_debug_pixel", i32, vp, sz, i32, i32, i32, i32, vp, i32)
 _sig("oracle_debug_path", i32, vp, sz, i32, i32, i32, i32, i32, vp)
 _sig("oracle_render_shard", i32, vp, sz, i32, i32, C.c_float, i32, i32, i32, i32, i32, i32, i32, vp,
      C.POINTER(OracleStats))
+_sig("oracle_render_iter", i32, vp, sz, i32, i32, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp,
+     C.POINTER(OracleStats))
 _sig("oracle_count_visits", i32, vp, sz, vp, sz, vp, vp, i32, i32, C.POINTER(C.c_double),
      C.POINTER(C.c_double), vp, sz)
 _sig("oracle_count_visits_q", i32, vp, sz, vp, sz, vp, vp, i32, i32, C.POINTER(C.c_double),
@@ -94,15 +96,30 @@ def _ieee_lib():
     return _ieee
 
 
-def render(blob: bytes, width, height, gamma=1.0, rect=None, threads=0, ieee_rcp=False):
-    """RGB_FLOAT32 image (H, W, 3) of the frame blob; pixels outside rect stay NaN."""
+def render(blob: bytes, width, height, gamma=1.0, rect=None, threads=0, ieee_rcp=False, iteration=0, accu=None):
+    """RGB_FLOAT32 image (H, W, 3) of the frame blob; pixels outside rect stay NaN.
+
+    iteration: the renderer's sampler iteration (rtRenderFrame(..., accumulate=1) raises it by one
+    per call). accu: None, or the framebuffer's accumulation buffer, float32 (H, W, 4), updated in
+    place; the image is then the running average. A new buffer is np.zeros."""
     threads = threads or cpu_count()
     x0, y0, x1, y1 = rect if rect is not None else (0, 0, width, height)
     out = np.full((height, width, 3), np.nan, np.float32)
     st = OracleStats()
-    lib = _ieee_lib() if ieee_rcp else _lib
-    rc = lib.oracle_render(blob, len(blob), width, height, gamma, x0, y0, x1, y1, threads, out.ctypes.data,
-                           C.byref(st))
+    if iteration == 0 and accu is None:
+        lib = _ieee_lib() if ieee_rcp else _lib
+        rc = lib.oracle_render(blob, len(blob), width, height, gamma, x0, y0, x1, y1, threads, out.ctypes.data,
+                               C.byref(st))
+    else:
+        if ieee_rcp:
+            raise ValueError("ieee_rcp renders iteration 0 without accumulation only")
+        if accu is not None and not (isinstance(accu, np.ndarray) and accu.dtype == np.float32 and
+                                     accu.shape == (height, width, 4) and accu.flags.c_contiguous and
+                                     accu.flags.writeable):
+            raise ValueError("accu: a writeable C-contiguous float32 array of shape (height, width, 4)")
+        rc = _lib.oracle_render_iter(blob, len(blob), width, height, gamma, x0, y0, x1, y1, 0, 1, threads,
+                                     int(iteration), accu.ctypes.data if accu is not None else None,
+                                     out.ctypes.data, C.byref(st))
     if rc != 0:
         raise RuntimeError(f"oracle_render: {_err()}")
     return out, {n: getattr(st, n) for n, _ in st._fields_}

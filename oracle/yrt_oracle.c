@@ -2367,6 +2367,7 @@ typedef struct {
   float gamma;
   uint32_t seed;
   float* out;
+  float* accu; /* AccuBuffer (x, y, z, w) per pixel, or NULL: a frame that does not accumulate */
   volatile int next;
   double nClosest, nShadow;
   pthread_mutex_t mu;
@@ -2406,8 +2407,19 @@ static void* worker(void* arg) {
           ray.time = J->T->t[(size_t)4 * J->T->rec + rec]; /* primary.time = sample.getTime() (:159) */
           L = add(L, Li(J->W, J->R, J->T, rec, ray, (uint32_t)(y * J->width + x), s, J->seed, fx, fy, &nc, &ns));
         }
-        /* AccuBuffer::update + DefaultToneMapper::eval */
-        V3 L0 = muls(L, rcp((float)spp));
+        /* AccuBuffer::update (api/framebuffer.h:289-304) + DefaultToneMapper::eval */
+        V3 L0;
+        if (J->accu) {
+          /* accu = true: next = cur + (L, spp), display next.xyz * rcp(next.w). A new buffer is the
+           * caller's zeros where the reference clears to (0, 0, 0, 1e-10): 1e-10 + spp == spp in
+           * float32 for every spp >= 1 (half an ulp of 1 is 6e-8), so the weights, and with them
+           * every later sum and reciprocal, are the same bits. */
+          float* a = &J->accu[((size_t)y * J->width + x) * 4];
+          a[0] = a[0] + L.x; a[1] = a[1] + L.y; a[2] = a[2] + L.z; a[3] = a[3] + (float)spp;
+          L0 = muls(v3(a[0], a[1], a[2]), rcp(a[3]));
+        } else {
+          L0 = muls(L, rcp((float)spp));
+        }
         if (J->gamma != 1.0f) {
           const float rg = rcp(J->gamma);
           L0 = v3(yrt_powf(L0.x, rg), yrt_powf(L0.y, rg), yrt_powf(L0.z, rg));
@@ -2689,6 +2701,16 @@ int oracle_render(const void* blob, size_t bytes, int width, int height, float g
 
 int oracle_render_shard(const void* blob, size_t bytes, int width, int height, float gamma, int x0, int y0, int x1,
                         int y1, int shardIndex, int shardCount, int threads, float* out, OracleStats* stats) {
+  return oracle_render_iter(blob, bytes, width, height, gamma, x0, y0, x1, y1, shardIndex, shardCount, threads, 0,
+                            NULL, out, stats);
+}
+
+/* IntegratorRenderer::renderFrame (integratorrenderer.cpp:63-69,88): the frame of sampler iteration
+ * `iteration`, added into accu4 where one is given */
+int oracle_render_iter(const void* blob, size_t bytes, int width, int height, float gamma, int x0, int y0, int x1,
+                       int y1, int shardIndex, int shardCount, int threads, int iteration, float* accu4, float* out,
+                       OracleStats* stats) {
+  if (iteration < 0) return fail("iteration must not be negative");
   if (shardCount < 1 || shardIndex < 0 || shardIndex >= shardCount) return -1;
   struct timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
@@ -2707,7 +2729,7 @@ int oracle_render_shard(const void* blob, size_t bytes, int width, int height, f
     return 0;
   }
   Table T;
-  table_build(&T, R.spp, R.sets, 0, R.maxDepth, 1 + R.maxDepth, R.filter, &W);
+  table_build(&T, R.spp, R.sets, iteration, R.maxDepth, 1 + R.maxDepth, R.filter, &W);
   uint8_t* sets = (uint8_t*)malloc((size_t)width * height);
   oracle_pixel_sets(width, height, T.sets, sets);
   Job J;
@@ -2721,6 +2743,7 @@ int oracle_render_shard(const void* blob, size_t bytes, int width, int height, f
   J.gamma = gamma;
   J.seed = B.seed;
   J.out = out;
+  J.accu = accu4;
   pthread_mutex_init(&J.mu, NULL);
   if (threads <= 0) threads = (int)sysconf(_SC_NPROCESSORS_ONLN);
   if (threads < 1) threads = 1;

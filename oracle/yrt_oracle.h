@@ -66,6 +66,15 @@ int oracle_render(const void* blob, size_t bytes, int width, int height, float g
 int oracle_render_shard(const void* blob, size_t bytes, int width, int height, float gamma, int x0, int y0, int x1,
                         int y1, int shardIndex, int shardCount, int threads, float* out_rgb, OracleStats* stats);
 
+/* oracle_render_shard at sampler iteration `iteration` (IntegratorRenderer::renderFrame's counter:
+ * the sample table and the precomputed light samples are built for it). accu4: NULL, or the
+ * frame's accumulation buffer, W*H*4 floats (x, y, z, weight) read and written in place: the
+ * pixel is then resolved as AccuBuffer::update(..., accu = true). A new buffer is all zeros.
+ * iteration 0 without accu4 is oracle_render_shard. */
+int oracle_render_iter(const void* blob, size_t bytes, int width, int height, float gamma, int x0, int y0, int x1,
+                       int y1, int shardIndex, int shardCount, int threads, int iteration, float* accu4,
+                       float* out_rgb, OracleStats* stats);
+
 /* Traces rays against the blob's scene: org4/dir4 as in yrtIntersect; hit4 = (t,u,v,tri)
  * (tri as int bits, -1 miss). anyHit != 0 -> occluded test, hit4.w = 1/0. */
 /* Debug: per-sample radiance Li of pixel (x, y), out3[3*s..] for s < min(spp, maxSpp); returns spp. */

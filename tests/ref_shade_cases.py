@@ -454,12 +454,25 @@ def oracle_light(typ, parms, xfm, P, s):
 # ---------------------------------------------------------------- the filtered sample table
 # (spp, iteration, num1D, num2D) at 64 sets: the shapes of test_sample_tables_without_filter
 TABLE_SHAPES = [(1, 0, 2, 3), (16, 0, 2, 3), (64, 0, 10, 11), (256, 0, 10, 11), (16, 5, 2, 3), (64, 3, 10, 11)]
+# the tables of progressive frames (rtRenderFrame(..., accumulate=1), tests/test_progressive.py): the
+# last iteration of a 64-sample chunk, the first and the second of the next one (spp 1: 63, 64, 65;
+# spp 16: 3, 4), and an spp the factory rounds up to a power of two (3 -> 4, offset 20)
+TABLE_SHAPES += [(1, 63, 2, 3), (1, 64, 2, 3), (1, 65, 2, 3), (16, 3, 2, 3), (16, 4, 2, 3), (3, 5, 2, 3)]
+
+
+def pow2_spp(spp):
+    """SamplerFactory's samplesPerPixel: spp rounded up to a power of two (samplers/sampler.cpp:91)."""
+    p = 1
+    while p < spp:
+        p <<= 1
+    return p
 
 
 def ref_sample_table(lib, spp, sets, iteration, n1, n2, bspline):
-    """The reference's own SamplerFactory::init table (dims, sets * spp), spp a power of two."""
-    out = np.zeros((5 + n1 + 2 * n2, sets * spp), F)
-    assert lib.ref_sample_table(spp, sets, iteration, n1, n2, int(bool(bspline)), _p(out)) == sets * spp
+    """The reference's own SamplerFactory::init table (dims, sets * pow2_spp(spp))."""
+    rec = sets * pow2_spp(spp)
+    out = np.zeros((5 + n1 + 2 * n2, rec), F)
+    assert lib.ref_sample_table(spp, sets, iteration, n1, n2, int(bool(bspline)), _p(out)) == rec
     return out
 
 

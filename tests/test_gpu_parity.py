@@ -411,7 +411,10 @@ def test_rgb8_framebuffer_quantization(gpu_device):
 
 
 def test_progressive_accumulate(gpu_device):
-    """rtRenderFrame(accumulate=1) averages successive frames (AccuBuffer, integratorrenderer.cpp:166)."""
+    """rtRenderFrame(accumulate=1) averages successive frames (AccuBuffer, integratorrenderer.cpp:166):
+    the second frame differs from the first, keeps its level, and both are the oracle's, bit for bit.
+    Every later iteration, the restart, the tone mapping of the average and the ownership of the
+    accumulation per framebuffer are pinned in tests/test_progressive.py."""
     s = _session(gpu_device, c1_args(64, 1))
     i = s.info()
     cam = s.camera()
@@ -422,6 +425,11 @@ def test_progressive_accumulate(gpu_device):
     b = d.framebuffer_array(i["framebuffer"], 64, 64, "RGB_FLOAT32")
     assert np.isfinite(b).all() and not np.array_equal(a, b)
     assert abs(float(b.mean()) - float(a.mean())) < 0.25 * float(a.mean()) + 1e-3
+    blob = s.export_frame(camera=cam)
+    accu = np.zeros((64, 64, 4), np.float32)
+    for k, img in enumerate((a, b)):
+        ref, _ = oracle.render(blob, 64, 64, i["gamma"], iteration=k, accu=accu)
+        parity(img, ref, 0.999)
     s.close()
 
 

@@ -55,12 +55,20 @@ def test_pixel_set_draw(w, h):
 
 
 @pytest.mark.parametrize("spp,iteration,n1,n2", [(1, 0, 2, 3), (16, 0, 2, 3), (64, 0, 10, 11), (256, 0, 10, 11),
-                                                 (16, 5, 2, 3), (64, 3, 10, 11)])
+                                                 (16, 5, 2, 3), (64, 3, 10, 11),
+                                                 # progressive frames: around the chunk boundary (64 samples),
+                                                 # and an spp that is no power of two
+                                                 (1, 63, 2, 3), (1, 64, 2, 3), (1, 65, 2, 3), (16, 3, 2, 3),
+                                                 (16, 4, 2, 3), (3, 5, 2, 3)])
 def test_sample_tables_without_filter(spp, iteration, n1, n2):
     sets = 64
     dims = 5 + n1 + 2 * n2
-    ref = _call("ref_sample_table_nofilter", (dims, sets * spp), np.float32, spp, sets, iteration, n1, n2)
+    # the replayed call pattern starts after SamplerFactory's constructor, which rounds spp up to a
+    # power of two (sampler.cpp:91; the real constructor runs in the filtered test below)
+    p2 = 1 << (spp - 1).bit_length()
+    ref = _call("ref_sample_table_nofilter", (dims, sets * p2), np.float32, p2, sets, iteration, n1, n2)
     got = oracle.sample_table(spp, sets, iteration, n1, n2, filter="none")
+    assert got.shape == ref.shape
     assert np.array_equal(ref.view(np.uint32), got.view(np.uint32))
 
 

@@ -90,7 +90,18 @@ struct GpuCtx {
   }
   Lane lanes[kMaxLanes];
   int numLanes = kDefaultLanes;
-  DevBuf dRp, dCam, dPixelSets, dAccu, dCount, dSpill, dSlab, dDirect;
+  DevBuf dRp, dCam, dPixelSets, dCount, dSpill, dSlab, dDirect;
+  // The (sum, weight) pixels the job's pixel resolve reads and writes (k_resolve_pixels): the
+  // framebuffer's own sums on this context (FrameBufferObj::accu) for a one-frame job; a
+  // multi-frame job never accumulates, so its frames' sums go to the scratch block dJobAccu
+  float4* accu = nullptr;
+  DevBuf dJobAccu;
+  // names this context in FrameBufferObj::Accu (an address could be a later context's)
+  const uint64_t serial = next_serial();
+  static uint64_t next_serial() {
+    static std::atomic<uint64_t> n{0};
+    return ++n;
+  }
   // denoise (yrtRenderGuides / yrtDenoiseFrameBuffer / yrtDenoiseCube), per face of the surface:
   // the guide frames, the filter's two ping-pong float4 frames, the modulation, the uploads of the
   // frames that live in host pixels and the FrameIO records; the cameras go to dCam
@@ -338,10 +349,14 @@ class Device {
               const std::vector<FrameBufferObj*>& F, int accumulate);
   // makes ctx[0]->blk a frame block no framebuffer holds unread frames in
   void rotate_frame_block();
+  // F's accumulation buffer on g, created cleared (enqueued on g's stream) at g's first frame
+  // into F; later frames only look it up
+  static float4* frame_accu(FrameBufferObj& F, GpuCtx& g);
   // Renders the tiles of shard (index, count) of the frame into g's full-size buffers (the other
-  // tiles' pixels are left zero when count > 1).
+  // tiles' pixels are left zero when count > 1). accu: the framebuffer's accumulation buffer on g
+  // (frame_accu) of a one-frame job, null for a multi-frame job or the debug renderer.
   void render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vector<CameraObj*>& C, ToneMapperObj& T,
-                    int W, int H, int index, int count, int accumulate, bool reportProgress);
+                    int W, int H, int index, int count, int accumulate, bool reportProgress, float4* accu);
   int gather_local(const SlabLayout& base, int numTiles);
   // the render's output is this shard alone (no gather fills the other shards' tiles): those
   // pixels must read as zeros, so per-shard images compose by sum

@@ -20,6 +20,7 @@
 
 #include "../common/yrt_gpu_types.h"
 #include "../common/yrt_math.h"
+#include "dev_buf.h"
 #include "parms.h"
 
 namespace yrt {
@@ -229,7 +230,19 @@ struct FrameBufferObj : Object {
   size_t stride = 0;
   std::vector<std::unique_ptr<HostPixels>> host;  // one per swapchain buffer (or user pointers)
   std::vector<void*> userPtrs;
-  std::vector<float> accu;                 // AccuBuffer (x,y,z,w) per pixel
+  // AccuBuffer (api/framebuffer.h:229-320), owned by the swap chain as in the reference
+  // (api/swapchain.h:44,121): (x, y, z, weight) per pixel in HBM, one buffer per GPU context that
+  // has rendered a frame into this framebuffer (GpuCtx::serial; a shard keeps the sums of its own
+  // tiles), created cleared at that context's first frame (Device::frame_accu) and released with
+  // the framebuffer.
+  struct Accu {
+    uint64_t ctxSerial = 0;
+    DevBuf sums;  // float4 [height][width]
+  };
+  std::vector<std::unique_ptr<Accu>> accu;
+  // the last frame came from a multi-frame job (rtRenderFrames), which keeps no per-framebuffer
+  // sums: rtRenderFrame(..., accumulate=1) is refused until a frame with accumulate=0
+  bool accuFromJob = false;
   // A frame still on the device (per buffer id): rtRenderFrame leaves it in HBM and
   // rtMapFrameBuffer copies it to the host pixels on first access (fb_read_back, device.cpp).
   struct Pending {

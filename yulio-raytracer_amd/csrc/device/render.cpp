@@ -42,6 +42,21 @@ void Device::rotate_frame_block() {
   }
 }
 
+float4* Device::frame_accu(FrameBufferObj& F, GpuCtx& g) {
+  for (const auto& a : F.accu)
+    if (a->ctxSerial == g.serial) return a->sums.as<float4>();
+  HIP_CHECK(hipSetDevice(g.hipDevice));
+  auto a = std::make_unique<FrameBufferObj::Accu>();
+  a->ctxSerial = g.serial;
+  const size_t bytes = (size_t)F.width * F.height * sizeof(float4);
+  a->sums.alloc(bytes);
+  // AccuBuffer::clear (api/framebuffer.h:268-272) stores the weight 1e-10, which the first frame's
+  // weight absorbs (1e-10 + spp == spp in float for spp >= 1): zeros give the same sums
+  HIP_CHECK(hipMemsetAsync(a->sums.p, 0, bytes, g.stream));
+  F.accu.push_back(std::move(a));
+  return F.accu.back()->sums.as<float4>();
+}
+
 void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& S, ToneMapperObj& T,
                     const std::vector<FrameBufferObj*>& F, int accumulate) {
   auto t0 = std::chrono::steady_clock::now();
@@ -81,17 +96,26 @@ void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& 
       return;
     }
     memset(&stats, 0, sizeof(stats));
+    // A multi-frame job resolves into a scratch block, not into its framebuffers' own sums, so
+    // there is nothing of its frame for a later frame to be averaged with
+    if (accumulate && nf == 1 && !R.debug && F[0]->accuFromJob)
+      throw std::runtime_error("rtRenderFrame: accumulate=1 on a framebuffer whose last frame came from a multi-frame "
+                               "job (rtRenderFrames keeps no accumulation): render it with accumulate=0 first");
     if (!accumulate) R.iteration = 0;
     rotate_frame_block();
     std::vector<GpuScene*> scenes(nr);
     for (int k = 0; k < nr; ++k) scenes[k] = &scene_on(S, ctx[k]->hipDevice, k == 0);
+    // the accumulation belongs to the framebuffer (found here, before the shards' threads start)
+    std::vector<float4*> accu(nr, nullptr);
+    if (nf == 1 && !R.debug)
+      for (int k = 0; k < nr; ++k) accu[k] = frame_accu(*F[0], *ctx[k]);
     // Without a process gather, the pixels of the other processes' shards (yrtSetTileShard)
     // must read as zeros so per-process images compose by sum: ctx[0]'s block is cleared
     // outside the tiles this call writes. With several devices in the process and no
     // process-level shard (shardCount 1), the local gather writes every tile: no clear.
     shardZero = !procGather && (nr == 1 || shardCount > 1);
     if (nr == 1) {
-      render_shard(*ctx[0], *scenes[0], R, C, T, W, H, shardIndex, shardCount, accumulate, true);
+      render_shard(*ctx[0], *scenes[0], R, C, T, W, H, shardIndex, shardCount, accumulate, true, accu[0]);
       tRendered = std::chrono::steady_clock::now();
     } else {
       // device k of this process renders the tiles t = shardIndex + k * shardCount (mod shardCount * N)
@@ -101,7 +125,7 @@ void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& 
         th.emplace_back([&, k] {
           try {
             render_shard(*ctx[k], *scenes[k], R, C, T, W, H, shardIndex + k * shardCount, shardCount * nr,
-                         accumulate, k == 0);
+                         accumulate, k == 0, accu[k]);
           } catch (const std::exception& e) {
             errs[k] = e.what();
           }
@@ -123,6 +147,8 @@ void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& 
   }
   if (!localErr.empty()) throw std::runtime_error(localErr);
   R.iteration++;
+  if (!R.debug)
+    for (FrameBufferObj* f : F) f->accuFromJob = nf > 1;
   for (int k = 0; k < nr; ++k) {
     const YRTRenderStats& s = ctx[k]->stats;
     stats.raysClosest += s.raysClosest;
@@ -332,10 +358,16 @@ static FrameView frame_view(GpuCtx& g, const RendererObj& R, const FrameCache& f
 }
 
 void Device::render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vector<CameraObj*>& C,
-                          ToneMapperObj& T, int W, int H, int index, int count, int accumulate, bool reportProgress) {
+                          ToneMapperObj& T, int W, int H, int index, int count, int accumulate, bool reportProgress,
+                          float4* accu) {
   const int nf = (int)C.size();
   HIP_CHECK(hipSetDevice(g.hipDevice));
   memset(&g.stats, 0, sizeof(g.stats));
+  g.accu = accu;
+  if (!g.accu && !R.debug) {
+    g.dJobAccu.alloc((size_t)nf * W * H * sizeof(float4));
+    g.accu = g.dJobAccu.as<float4>();
+  }
   ShardSetup s;
   s.sw = RenderSwitches::read();
   s.index = index;

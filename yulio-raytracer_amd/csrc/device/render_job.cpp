@@ -55,7 +55,6 @@ ShardJob::ShardJob(const Device& D, GpuCtx& g, const GpuScene& G, RendererObj& R
 void ShardJob::prepare_lanes() {
   const GpuRenderParams& rp = s.rp;
   const int nl = plan.lanes;
-  g.dAccu.alloc((size_t)rp.numFrames * rp.width * rp.height * 16);
   g.ensure_streams(nl);
   for (int l = 0; l < nl; ++l) {
     Lane& L = g.lanes[l];
@@ -242,7 +241,7 @@ void ShardJob::enqueue_step(Lane& L, LaneJob& J) {
     Pd.seq = J.seq;
     L.pendCount += 1;
     launch_resolve_pixels(fv, pb, bi, g.fbFloat(), g.fbRGB8(), (int)rgb8_row_stride(s.rp.width),
-                          g.dAccu.as<float4>(), s.accumulate ? 1 : 0, st);
+                          g.accu, s.accumulate ? 1 : 0, st);
     J.active = false;
   }
   J.step += 1;
