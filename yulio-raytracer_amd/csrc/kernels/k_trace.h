@@ -14,12 +14,17 @@ namespace yrt {
 // their ray, those lanes take the next rays of the chunk (ballot + popcount, no atomics).
 // This keeps 64-wide waves busy although ray costs differ by 10-100x. Same visit order and
 // the same (t, triangle id) closest-hit rule as closest_hit (yrt_traverse.h).
+// Nothing global is loaded and waited for between the loop head and the node / leaf step: what
+// a finished query owes to memory is paid at the refill, in one batch for the refilling lanes —
+// closest hit stores its hit record there; any hit with the fused shadow resolve adds its
+// unoccluded rays' light there (shadow_done; profiles/shadow_resolve_at_refill.txt).
 #ifndef YRT_REFILL
 #define YRT_REFILL 40  // 24/6 +1.3 % over 16/4; with 64-lane blocks 28/6 +0.4 %, then 40/8 +0.9 % over 28/6;
                         // with four lanes 48 everywhere: C4 -0.8 %, C3 +0.2 %, C5 +1.6 % (r05cc/dd/ee)
 #endif
 #ifndef YRT_REFILL_ANY
-#define YRT_REFILL_ANY 32  // any hit: with node bias 20, C3 +1.5 %, C4 / C5 within the spread (r05ii)
+#define YRT_REFILL_ANY 32  // any hit: with node bias 20, C3 +1.5 %, C4 / C5 within the spread (r05ii); with the
+                           // resolve at the refill 24 loses 1.7 ms on C3, 40 is within the spread (-0.3 ms)
 #endif
 #ifndef YRT_REFILL_PRIM
 #define YRT_REFILL_PRIM YRT_REFILL  // refill threshold of the fused depth-0 instantiation
@@ -67,19 +72,19 @@ constexpr int kTriStep = 2;  // triangles per lane per leaf step: 2 is +0.7 % ov
 #define YRT_PROF(i, v) ((void)0)
 #endif
 
-// A finished shadow query: the occlusion flag, or (fused, PathBuffers::fuseShadow) the
-// light's contribution added to its path's radiance when unoccluded (k_shadow_resolve order).
-__device__ __forceinline__ void shadow_done(const ShadowFuse& sf, int* __restrict__ occOut, int q, bool occluded) {
+// A finished shadow query. Not fused: its occlusion flag is stored. Fused (PathBuffers::
+// fuseShadow, one light): an unoccluded ray's contribution is added to its path's radiance
+// (k_shadow_resolve's operations), but not here: the lane keeps its slot in q ("pending") and
+// the kernel resolves it at its next refill or at the wave's end, as the closest-hit
+// instantiation stores its hits; q = -1: occluded, nothing to add. The two dependent loads of
+// the sum (contrib[q], then pathL[contrib[q].w]) miss L2, and waited for here, inside the
+// traversal loop, they would stop the lanes still traversing once per unoccluded ray.
+__device__ __forceinline__ void shadow_done(const ShadowFuse& sf, int* __restrict__ occOut, int& q, bool occluded) {
   if (sf.contrib) {
-    if (!occluded) {
-      const float4 c = sf.contrib[q];
-      const int tg = __float_as_int(c.w);
-      float4* Lp = sf.pathL + tg;
-      const float4 l = *Lp;
-      *Lp = make_float4(l.x + c.x, l.y + c.y, l.z + c.z, l.w);
-    }
+    if (occluded) q = -1;
   } else {
     occOut[q] = occluded ? 1 : 0;
+    q = -1;
   }
 }
 
@@ -226,6 +231,31 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu
       hitOut[q] = make_float4(best.t, best.u / bestDen, best.v / bestDen, __int_as_float(best.tri)); \
     q = -1;                                                                                          \
   } while (0)
+  // a refilled lane's traversal state from its ray (ro, rd); NaN tfar (tMaxShadowRay = inf,
+  // SURVEY App. A Q4): no hit, nothing to traverse
+#define YRT_RAY_SETUP()                                                                   \
+  do {                                                                                    \
+    ri = make_float4(safe_inv(rd.x), safe_inv(rd.y), safe_inv(rd.z), 0.f);                \
+    ri.w = __int_as_float(plane_offsets(ri.x, ri.y, ri.z));                               \
+    {                                                                                     \
+      V3 oi;                                                                              \
+      float mg;                                                                           \
+      ray_slab_consts(v3(ro.x, ro.y, ro.z), v3(ri.x, ri.y, ri.z), oi, mg);                \
+      rc = make_float4(oi.x, oi.y, oi.z, mg);                                             \
+    }                                                                                     \
+    best.t = rd.w;                                                                        \
+    best.u = best.v = 0.f;                                                                \
+    best.tri = -1;                                                                        \
+    bestDen = 1.f;                                                                        \
+    sp = 0;                                                                               \
+    curIdx = 0;                                                                           \
+    curCnt = 0;                                                                           \
+    pendCnt = 0;                                                                          \
+    has = rd.w >= ro.w;                                                                   \
+    if (!has) {                                                                           \
+      if (ANY) shadow_done(sf, occOut, q, false);                                         \
+    }                                                                                     \
+  } while (0)
 
 #ifdef YRT_PROFILE
   unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -244,6 +274,44 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu
       if (next < end) {
         const unsigned li = next + lanes_below(idle);
         if (!has) {
+          if constexpr (ANY) {
+            // Fused: the pending lanes (q >= 0, see shadow_done) are resolved here. Their
+            // contributions are loaded beside the new rays (one wait for both), their paths'
+            // radiance before the new rays' setup arithmetic, which covers part of that second
+            // round trip; the sum is stored last. The same l + c per channel as
+            // k_shadow_resolve, one writer per path and launch.
+            const bool resolve = sf.contrib && q >= 0;
+            const bool take = li < end;
+            // read under `resolve` only; set here all the same: left unset, the kernel spills
+            // (44 B of scratch at 64 VGPRs)
+            float4 c = make_float4(0.f, 0.f, 0.f, 0.f), l = c;
+            float4* Lp = nullptr;
+            if (resolve) c = sf.contrib[q];
+            q = -1;
+            if (take) {
+              q = qmap_phys(qm, segCap, li);
+              ro = org[q];
+              rd = dir[q];
+              if (MOTION) rtime = rayTime[q];
+            }
+            // One wait for the contributions and the rays, here and on every path: the path id
+            // and tfar are pinned as first used at this point. Without the pins the path id's
+            // address arithmetic, and its wait with it, moves up to the contribution's load, and
+            // the rays' wait into the setup below, behind the radiance's load.
+            int tg = __float_as_int(c.w);
+            asm volatile("" : "+v"(tg), "+v"(rd.w));
+            if (resolve) {
+              Lp = sf.pathL + tg;
+              l = *Lp;
+            }
+            if (take) {
+              // a ray with nothing to traverse and not fused: its flag is stored at once;
+              // fused, it is pending like any unoccluded ray (has = false, q kept)
+              YRT_RAY_SETUP();
+            }
+            asm volatile("" : "+v"(l.x));  // the radiance's wait, on every path too
+            if (resolve) *Lp = make_float4(l.x + c.x, l.y + c.y, l.z + c.z, l.w);
+          } else {
           if (!ANY && q >= 0) YRT_STORE_HIT();
           if (li < end) {
             if constexpr (PRIM) {
@@ -288,32 +356,22 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu
             rd = dir[q];
             if (MOTION) rtime = rayTime[q];
             }
-            ri = make_float4(safe_inv(rd.x), safe_inv(rd.y), safe_inv(rd.z), 0.f);
-            ri.w = __int_as_float(plane_offsets(ri.x, ri.y, ri.z));
-            {
-              V3 oi;
-              float mg;
-              ray_slab_consts(v3(ro.x, ro.y, ro.z), v3(ri.x, ri.y, ri.z), oi, mg);
-              rc = make_float4(oi.x, oi.y, oi.z, mg);
-            }
-            best.t = rd.w;
-            best.u = best.v = 0.f;
-            best.tri = -1;
-            bestDen = 1.f;
-            sp = 0;
-            curIdx = 0;
-            curCnt = 0;
-            pendCnt = 0;
-            // NaN tfar (tMaxShadowRay = inf): no hit, nothing to traverse
-            has = rd.w >= ro.w;
-            if (!has) {
-              if (ANY) shadow_done(sf, occOut, q, false);
-            }
+            YRT_RAY_SETUP();
+          }
           }
         }
         next += (unsigned)nIdle;
       } else if (nIdle == 64) {
         if (!ANY && q >= 0) YRT_STORE_HIT();
+        if constexpr (ANY) {
+          // the lanes still pending when the chunk is used up
+          if (sf.contrib && q >= 0) {
+            const float4 c = sf.contrib[q];
+            float4* Lp = sf.pathL + __float_as_int(c.w);
+            const float4 l = *Lp;
+            *Lp = make_float4(l.x + c.x, l.y + c.y, l.z + c.z, l.w);
+          }
+        }
         if constexpr (PRIM) {
           // the camera rays this wave traced: the valid path ids of its chunk (the refill's
           // test again, after the loop, so that no count is carried through it)
@@ -493,6 +551,7 @@ __global__ __launch_bounds__(YRT_TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu
 #undef YRT_PUSH
 #undef YRT_POP
 #undef YRT_STORE_HIT
+#undef YRT_RAY_SETUP
 #undef YRT_NNODE
 #undef YRT_NBLOCKED
 #undef YRT_PROF
