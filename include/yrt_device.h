@@ -429,6 +429,18 @@ YRT_API int yrtDebugDirTerms(YRTDevice dev, int mode, const float* u, const floa
  * (common/yrt_tile_scatter.h: a fixed bijection of [0, T), used by the renderer and the gather
  * whenever the tile stride is above 1). Host-side; -1 for t outside [0, T). */
 YRT_API int yrtDebugTileScatter(int t, int T);
+/* Test-only probe of the multi-GPU gather's two kernels (k_pack_tiles, k_unpack_tiles,
+ * kernels/k_tiles.h), launched exactly as the gathers launch them, on host buffers: fbFloat is
+ * numFrames stacked frames of height x width x 3 floats, fbRGB8 the same frames as byte rows of
+ * (3 * width rounded up to 4) bytes, slab numTiles * 256 elements (4 bytes each with rgb8, else 16).
+ * All three are uploaded; op 0 packs the shard's tiles (job tile = tileOffset + j * tileStride,
+ * j < numTiles) and copies the slab back, op 1 unpacks the slab and copies both frame arrays
+ * back. Refused without a launch: a host-only device, non-positive sizes, tileOffset < 0,
+ * tileStride < 1, an op other than 0 / 1, more tiles than the shard holds, or a host buffer
+ * (sizes in bytes) smaller than the job. Not part of the renderer. */
+YRT_API int yrtDebugTileSlab(YRTDevice dev, int width, int height, int numFrames, int rgb8, int tileOffset,
+                             int tileStride, int numTiles, int op, float* fbFloat, size_t fbFloatBytes,
+                             uint8_t* fbRGB8, size_t fbRGB8Bytes, void* slab, size_t slabBytes);
 /* The batch plan of a wavefront job over shardTiles tiles at spp samples per pixel: how a
  * device with `lanes` lanes and a batch capacity of `capacity` paths (yrtSetBatchCapacity)
  * cuts the job into batches. capture != 0: a ray-capture frame (yrtSetRayCapture); grow: the

@@ -383,6 +383,55 @@ int yrtDebugTileScatter(int t, int T) {
   return yrt_tile_scatter(t, T);
 }
 
+int yrtDebugTileSlab(YRTDevice dev, int width, int height, int numFrames, int rgb8, int tileOffset, int tileStride,
+                     int numTiles, int op, float* fbFloat, size_t fbFloatBytes, uint8_t* fbRGB8, size_t fbRGB8Bytes,
+                     void* slab, size_t slabBytes) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  if (width < 1 || height < 1 || numFrames < 1 || width > (1 << 20) || height > (1 << 20) || numTiles < 0 ||
+      tileStride < 1 || tileOffset < 0 || (op != 0 && op != 1) || !fbFloat || !fbRGB8 || !slab)
+    throw std::runtime_error("yrtDebugTileSlab: invalid arguments");
+  const int64_t tilesPerFrame = (int64_t)((width + 15) / 16) * ((height + 15) / 16);
+  const int64_t total = tilesPerFrame * numFrames;
+  if (total * 256 > INT32_MAX)
+    throw std::runtime_error("yrtDebugTileSlab: the job's pixels do not fit the kernels' int index");
+  // numTiles <= shard_tiles(total, tileOffset, tileStride), in 64 bits (any stride): the last
+  // tile the kernels address, tileOffset + (numTiles - 1) * tileStride, is a tile of the job
+  if (numTiles > 0 && (int64_t)tileOffset + (int64_t)(numTiles - 1) * tileStride >= total)
+    throw std::runtime_error("yrtDebugTileSlab: numTiles exceeds the shard's tiles");
+  const size_t floatBytes = (size_t)numFrames * height * width * 3 * sizeof(float);
+  const size_t rgb8Bytes = GpuCtx::FrameBlock::rgb8_bytes(width, height, numFrames);
+  const size_t needSlab = (size_t)numTiles * 256 * slab_element_bytes(rgb8 ? 1 : 0);
+  if (fbFloatBytes < floatBytes || fbRGB8Bytes < rgb8Bytes || slabBytes < needSlab)
+    throw std::runtime_error("yrtDebugTileSlab: a host buffer is smaller than the job");
+  const SlabLayout L{width, height, (int)rgb8_row_stride(width), (int)tilesPerFrame, tileOffset, tileStride,
+                     rgb8 ? 1 : 0, 0};
+  // the arguments are judged first, so a host-only device refuses the invalid ones for their own reason
+  if (!D.gpu) throw std::runtime_error("yrtDebugTileSlab: host-only device");
+  HIP_CHECK(hipSetDevice(D.hipDevice));
+  DevBuf dF, dB, dS;
+  dF.alloc(floatBytes);
+  dB.alloc(rgb8Bytes);
+  dS.alloc(slabBytes);  // the caller's whole slab travels: what lies behind the shard's elements returns as it went
+  HIP_CHECK(hipMemcpy(dF.p, fbFloat, floatBytes, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(dB.p, fbRGB8, rgb8Bytes, hipMemcpyHostToDevice));
+  if (slabBytes) HIP_CHECK(hipMemcpy(dS.p, slab, slabBytes, hipMemcpyHostToDevice));
+  if (op == 0) {
+    launch_pack_tiles(dF.as<float>(), dB.as<uint8_t>(), L, numTiles, dS.p, 0);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    if (slabBytes) HIP_CHECK(hipMemcpy(slab, dS.p, slabBytes, hipMemcpyDeviceToHost));
+  } else {
+    launch_unpack_tiles(dS.p, dF.as<float>(), dB.as<uint8_t>(), L, numTiles, 0);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(fbFloat, dF.p, floatBytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(fbRGB8, dB.p, rgb8Bytes, hipMemcpyDeviceToHost));
+  }
+  return 0;
+  DEV_END(-1)
+}
+
 int yrtDebugCubeTap(int W, int face, int qx, int qy, int* g, int* x, int* y) {
   if (!g || !x || !y) return -1;
   return yrt_cube_tap(W, face, qx, qy, g, x, y);

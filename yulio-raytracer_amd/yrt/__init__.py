@@ -316,6 +316,19 @@ class Device:
         return out
 
     # -- rendering (device.h:223-234)
+    def debug_tile_slab(self, op, fb_float, fb_rgb8, slab, width, height, frames, rgb8, offset, stride, num_tiles):
+        """yrtDebugTileSlab, the test-only probe of the gather's kernels: op 0 packs the shard's tiles
+        of the frames into `slab`, op 1 unpacks `slab` into the frames, in place. fb_float float32 /
+        uint32 (frames, height, width, 3), fb_rgb8 uint8 (frames, height, row stride), slab uint32
+        (num_tiles * 256,) with rgb8, else (num_tiles * 256, 4): C-contiguous arrays."""
+        for a in (fb_float, fb_rgb8, slab):
+            if not (a.flags.c_contiguous and a.flags.writeable):
+                raise ValueError("debug_tile_slab: C-contiguous writeable arrays")
+        self._rc(N.dev.yrtDebugTileSlab(self.h, int(width), int(height), int(frames), int(bool(rgb8)), int(offset),
+                                        int(stride), int(num_tiles), int(op), fb_float.ctypes.data, fb_float.nbytes,
+                                        fb_rgb8.ctypes.data, fb_rgb8.nbytes, slab.ctypes.data, slab.nbytes),
+                 "yrtDebugTileSlab")
+
     def rtRenderFrame(self, renderer, camera, scene, toneMapper, frameBuffer, accumulate=0):
         self._rc(N.dev.yrtRenderFrame(self.h, renderer, camera, scene, toneMapper, frameBuffer, int(accumulate)),
                  "rtRenderFrame")

@@ -195,6 +195,10 @@ try:  # round 6; absent from older tuning builds selected with YRT_LIB_DIR
     _sig(dev, "yrtDebugTileScatter", i32, i32, i32)
 except AttributeError:
     pass
+try:  # the gather kernels' probe; absent from older builds selected with YRT_LIB_DIR
+    _sig(dev, "yrtDebugTileSlab", i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp, sz)
+except AttributeError:
+    pass
 try:  # absent from older builds selected with YRT_LIB_DIR
     _sig(dev, "yrtDebugBatchPlan", i32, C.c_int64, i32, C.c_int64, i32, i32, i32, C.POINTER(C.c_int64))
 except AttributeError:
