@@ -220,6 +220,16 @@ YRT_API int yrtIntersect(YRTDevice dev, YRTHandle scene, const float* org4, cons
                          float* hit4, void* stream);
 YRT_API int yrtOccluded(YRTDevice dev, YRTHandle scene, const float* org4, const float* dir4, uint32_t n,
                         int32_t* occluded, void* stream);
+/* The same queries with a time per ray (Ray::time): time[i], n floats in device memory. On a scene
+ * with moving geometry (a mesh with "motions", a sphere with dPdt) ray i meets every triangle at
+ * p + time[i] * m. time[i] lies in [0, 1], the span the BVH's boxes cover; a value outside it or
+ * a NaN is outside the contract (the result is unspecified). A scene without moving geometry
+ * ignores the times, as a static mesh ignores Ray::time: the array is accepted and not read.
+ * time = NULL is the untimed call, and the untimed call on a moving scene is time 0 for every ray. */
+YRT_API int yrtIntersectTimed(YRTDevice dev, YRTHandle scene, const float* org4, const float* dir4,
+                              const float* time, uint32_t n, float* hit4, void* stream);
+YRT_API int yrtOccludedTimed(YRTDevice dev, YRTHandle scene, const float* org4, const float* dir4,
+                             const float* time, uint32_t n, int32_t* occluded, void* stream);
 /* Maps a global triangle id (hit4.w) to Embree's (geomID, primID). */
 YRT_API int yrtTriangleIds(YRTDevice dev, YRTHandle scene, int32_t tri, int32_t* geomID, int32_t* primID);
 

@@ -44,6 +44,7 @@ def _sig(name, res, *args):
 
 _sig("oracle_render", i32, vp, sz, i32, i32, C.c_float, i32, i32, i32, i32, i32, vp, C.POINTER(OracleStats))
 _sig("oracle_trace", i32, vp, sz, vp, vp, i32, i32, vp)
+_sig("oracle_trace_time", i32, vp, sz, vp, vp, vp, i32, i32, vp)
 _sig("oracle_debug_pixel", i32, vp, sz, i32, i32, i32, i32, vp, i32)
 _sig("oracle_debug_path", i32, vp, sz, i32, i32, i32, i32, i32, vp)
 _sig("oracle_render_shard", i32, vp, sz, i32, i32, C.c_float, i32, i32, i32, i32, i32, i32, i32, vp,
@@ -159,12 +160,20 @@ def debug_path(blob: bytes, width, height, x, y, sample):
     return out[: int((out[:, 0] != 0).sum())]
 
 
-def trace(blob: bytes, org4: np.ndarray, dir4: np.ndarray, any_hit=False):
+def trace(blob: bytes, org4: np.ndarray, dir4: np.ndarray, any_hit=False, time=None):
+    """time: None (every ray at Ray's default time 0) or one Ray::time in [0, 1] per ray."""
     org4 = np.ascontiguousarray(org4, np.float32)
     dir4 = np.ascontiguousarray(dir4, np.float32)
     n = org4.shape[0]
     hit = np.zeros((n, 4), np.float32)
-    rc = _lib.oracle_trace(blob, len(blob), org4.ctypes.data, dir4.ctypes.data, n, int(any_hit), hit.ctypes.data)
+    if time is None:
+        rc = _lib.oracle_trace(blob, len(blob), org4.ctypes.data, dir4.ctypes.data, n, int(any_hit), hit.ctypes.data)
+    else:
+        time = np.ascontiguousarray(time, np.float32)
+        if time.shape != (n,):
+            raise ValueError("time: one float per ray")
+        rc = _lib.oracle_trace_time(blob, len(blob), org4.ctypes.data, dir4.ctypes.data, time.ctypes.data, n,
+                                    int(any_hit), hit.ctypes.data)
     if rc != 0:
         raise RuntimeError(f"oracle_trace: {_err()}")
     return hit

@@ -2823,6 +2823,11 @@ static int debug_pixel_impl(const void* blob, size_t bytes, int width, int heigh
 }
 
 int oracle_trace(const void* blob, size_t bytes, const float* org4, const float* dir4, int n, int anyHit, float* hit4) {
+  return oracle_trace_time(blob, bytes, org4, dir4, NULL, n, anyHit, hit4);
+}
+
+int oracle_trace_time(const void* blob, size_t bytes, const float* org4, const float* dir4, const float* time, int n,
+                      int anyHit, float* hit4) {
   Blob B;
   if (blob_parse(blob, bytes, &B)) return -1;
   World W;
@@ -2830,6 +2835,7 @@ int oracle_trace(const void* blob, size_t bytes, const float* org4, const float*
   for (int i = 0; i < n; ++i) {
     Ray r = {v3(org4[4 * i], org4[4 * i + 1], org4[4 * i + 2]), v3(dir4[4 * i], dir4[4 * i + 1], dir4[4 * i + 2]),
              org4[4 * i + 3], dir4[4 * i + 3]};
+    if (time) r.time = time[i]; /* else Ray's default time 0 (ray.h:33) */
     Hit h = trace(&W, &r, anyHit);
     if (anyHit) {
       hit4[4 * i] = hit4[4 * i + 1] = hit4[4 * i + 2] = 0.f;

@@ -84,6 +84,10 @@ int oracle_debug_pixel(const void* blob, size_t bytes, int width, int height, in
 int oracle_debug_path(const void* blob, size_t bytes, int width, int height, int x, int y, int sample, float* out);
 int oracle_trace(const void* blob, size_t bytes, const float* org4, const float* dir4, int n, int anyHit,
                  float* hit4);
+/* oracle_trace with Ray::time set per ray: time[i], n floats in [0, 1] (NULL: every ray keeps
+ * Ray's default time 0). Moving triangles are met at p + time * m; static ones ignore it. */
+int oracle_trace_time(const void* blob, size_t bytes, const float* org4, const float* dir4, const float* time, int n,
+                      int anyHit, float* hit4);
 
 /* Counts node/triangle visits of the GPU's own BVH (exported by yrtExportBVH) for the given
  * closest-hit rays (traversal order of the device kernel, restated). Used for the roofline's

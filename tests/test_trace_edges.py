@@ -1,6 +1,8 @@
 """The ray-query kernel (kernels/k_trace.h) where random rays never take it: the spill of its
 16-entry LDS ring stack to global memory, lane refill with unaligned chunks, and the rules that
 hold only on exact equality (ties, range edges, den == 0, zero direction components).
+Everything here runs the static instantiations (MOTION = false); tests/test_trace_motion.py does
+the same for the moving-geometry ones, through the timed calls.
 
 References: a brute-force test of every ray against every triangle in numpy float32
 (trace_scenes.brute_force, no BVH and so no box test of any kind), the oracle's own trace, and,

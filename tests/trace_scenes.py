@@ -1,5 +1,6 @@
 """Scenes, rays and a brute-force reference for the ray-query kernel's edge tests
-(tests/test_trace_edges.py), and the scene, poses and rays of the refit tests (tests/test_refit.py).
+(tests/test_trace_edges.py; tests/test_trace_motion.py for moving geometry), and the scene, poses
+and rays of the refit tests (tests/test_refit.py).
 
 Everything is built through the device API (rtNewShape("trianglemesh"), positions, indices), so
 the same builders serve the host-only device of the CPU tests and the MI355X.
@@ -15,8 +16,11 @@ INF = np.float32(np.inf)
 # ----------------------------------------------------------------------------- scene building
 class MeshScene:
     """A committed scene of triangle meshes (one Matte material, optionally an ambient light) and a
-    pinhole camera. meshes: [(positions (n, 3), indices (m, 3), cullBackFaces[, normals (n, 3)])] in
-    primitive-slot order; global triangle ids count through the meshes in that order."""
+    pinhole camera. meshes: [(positions (n, 3), indices (m, 3), cullBackFaces[, normals (n, 3)
+    or None[, motions (n, 3) or None]])] in primitive-slot order; global triangle ids count through
+    the meshes in that order. A mesh with motions (the "motions" float3 array: the vertex at ray
+    time t is p + t * m) makes the scene a moving one; tri9 then holds the vertices at time 0 and
+    mot9 their motions, zeros for the meshes without."""
 
     def __init__(self, dev, meshes, eye=(0, 0, -10), look=(0, 0, 0), up=(0, 1, 0), angle=60.0, light=None):
         from test_cpu_host import yrt_lookat
@@ -28,8 +32,11 @@ class MeshScene:
         self.meshes = []
         for slot, m in enumerate(meshes):
             pos, idx, cull = m[:3]
-            self.meshes.append({"idx": np.ascontiguousarray(idx, np.int32), "cull": bool(cull)})
+            mot = m[4] if len(m) > 4 else None
+            self.meshes.append({"idx": np.ascontiguousarray(idx, np.int32), "cull": bool(cull),
+                                "mot": None if mot is None else np.ascontiguousarray(mot, F)})
             self._set_mesh(slot, pos, m[3] if len(m) > 3 else None)
+        self.has_motion = any(m["mot"] is not None for m in self.meshes)
         if light is not None:
             amb = d.rtNewLight("ambientlight")
             d.rtSetFloat3(amb, "L", light, light, light)
@@ -53,6 +60,9 @@ class MeshScene:
         if nor is not None:
             d.rtSetArray(mesh, "normals", "float3", d.rtNewData("immutable", nor), len(nor), 12)
         d.rtSetArray(mesh, "indices", "int3", d.rtNewData("immutable", idx), len(idx), 12)
+        if m["mot"] is not None:
+            assert m["mot"].shape == pos.shape
+            d.rtSetArray(mesh, "motions", "float3", d.rtNewData("immutable", m["mot"]), len(pos), 12)
         if m["cull"]:
             d.rtSetBool1(mesh, "cullBackFaces", True)
         d.rtCommit(mesh)
@@ -63,6 +73,12 @@ class MeshScene:
         self.dev.rtCommit(self.scene)
         self.tri9 = np.concatenate([m["pos"][m["idx"]].reshape(-1, 9) for m in self.meshes]).astype(F)  # v0 v1 v2 by id
         self.flags = np.concatenate([np.full(len(m["idx"]), 1 if m["cull"] else 0, np.uint32) for m in self.meshes])
+        self.mot9 = np.concatenate([(np.zeros_like(m["pos"]) if m["mot"] is None else m["mot"])[m["idx"]].reshape(-1, 9)
+                                    for m in self.meshes]).astype(F)
+        if self.has_motion:
+            # no -0.0 among the coordinates and motions: p + 0 * m is then p bit for bit
+            for a in (self.tri9, self.mot9):
+                assert not np.signbit(a[a == 0]).any()
         self.info = self.dev.scene_info(self.scene)
         self.blob = self.frame("debug")[1]
 
@@ -118,25 +134,40 @@ def _dot(a, b):
     return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
 
 
-def brute_force(tri9, flags, org4, dir4, block=2048):
+def brute_force(tri9, flags, org4, dir4, mot9=None, time=None, block=2048):
     """Every ray against every triangle, no BVH, float32 operation for operation as the kernel's
     tri_test_g and the oracle's tri_test state it (separate multiplies and adds, t = T / |den|,
     the cull flag). Returns (hit (n, 4) float32: t, u, v, id bits of the smallest (t, id) among
-    the accepted triangles with tnear < t < tfar, or tfar, 0, 0, -1; occluded (n,) int32)."""
+    the accepted triangles with tnear < t < tfar, or tfar, 0, 0, -1; occluded (n,) int32).
+    time (n,), with mot9: every ray sees every triangle at its own time, the vertices p + time * m
+    as a float32 product and then a float32 sum (two roundings, as tri_at and the oracle's trace
+    state it), e1 = p0 - p1 and e2 = p2 - p0 from those. The block of rays then shrinks so that its
+    (rays x triangles x 9) vertex array stays within 64 MB."""
     tri9 = np.ascontiguousarray(tri9, F)
     org4 = np.ascontiguousarray(org4, F)
     dir4 = np.ascontiguousarray(dir4, F)
     n, T = len(org4), len(tri9)
-    v0 = [tri9[None, :, k] for k in range(3)]
-    e1 = [tri9[None, :, k] - tri9[None, :, 3 + k] for k in range(3)]
-    e2 = [tri9[None, :, 6 + k] - tri9[None, :, k] for k in range(3)]
-    Ng = _cross(e1, e2)
+    if time is not None:
+        time = np.ascontiguousarray(time, F)
+        mot9 = np.ascontiguousarray(mot9, F)
+        assert time.shape == (n,) and mot9.shape == tri9.shape
+        block = max(1, min(block, (64 << 20) // (36 * max(T, 1))))
     cull = (np.asarray(flags)[None, :] & 1) != 0
     hit = np.zeros((n, 4), F)
     occ = np.zeros(n, np.int32)
     one = F(1.0)
     with np.errstate(all="ignore"):
         for b in range(0, n, block):
+            if time is None:
+                p = tri9[None, :, :]
+            else:
+                prod = time[b:b + block, None, None] * mot9[None, :, :]
+                p = tri9[None, :, :] + prod
+                assert prod.dtype == F and p.dtype == F
+            v0 = [p[:, :, k] for k in range(3)]
+            e1 = [p[:, :, k] - p[:, :, 3 + k] for k in range(3)]
+            e2 = [p[:, :, 6 + k] - p[:, :, k] for k in range(3)]
+            Ng = _cross(e1, e2)
             o = [org4[b:b + block, k, None] for k in range(3)]
             d = [dir4[b:b + block, k, None] for k in range(3)]
             tnear, tfar = org4[b:b + block, 3, None], dir4[b:b + block, 3, None]
@@ -211,17 +242,20 @@ def chain_mesh(n=CHAIN_N, r=CHAIN_R, seed=7):
 CHAIN_WALL = 200  # global id of the backstop triangle
 
 
-def chain_scene(dev):
+def chain_scene(dev, wall_motion=None):
     """The chain and, as a second mesh, a backstop triangle across the axis at x = 1.5 (beyond the
     coarse end): rays along the axis hit nothing but it. For +x rays from the fine end it is the
     farthest box, for -x any-hit rays from x = 2 the nearest, so either order pushes it first and
     pops it last: the hit is found only if the bottom of the stack survives the deep descent.
     The camera sits just before the fine end and looks along +x (24 degrees: the central rays run
-    the whole chain, the outer ones hit its triangles)."""
+    the whole chain, the outer ones hit its triangles).
+    wall_motion: the backstop's three vertices get this motion (the chain itself stays unmoved),
+    which makes the scene a moving one."""
     pos, idx = chain_mesh()
     w = 0.5
     wall = np.array([[1.5, -w, -w], [1.5, 2 * w, -w], [1.5, -w, 2 * w]], F)
-    return MeshScene(dev, [(pos, idx, False), (wall, np.array([[0, 1, 2]], np.int32), False)],
+    mot = None if wall_motion is None else np.tile(np.asarray(wall_motion, F), (3, 1))
+    return MeshScene(dev, [(pos, idx, False), (wall, np.array([[0, 1, 2]], np.int32), False, None, mot)],
                      eye=(-1e-7, 0, 0), look=(1, 0, 0), up=(0, 1, 0), angle=24.0, light=2.0)
 
 
@@ -259,6 +293,30 @@ def chain_rays(tri9, n=4096, seed=11):
     org[m, :3] = o
     dr[m, :3] = v / np.linalg.norm(v, axis=1, keepdims=True)
     return org, dr, kind
+
+
+CHAIN_WALL_MOTION = (0.0, 2.0, 0.0)  # the backstop's lower edge y = -0.5 + 2 * time reaches the axis at time 0.25
+
+
+def moving_chain_scene(dev):
+    """chain_scene with the backstop moving by CHAIN_WALL_MOTION: the axis passes through it only
+    for time <= 0.25 (at exactly 0.25 its edge lies on the axis, and the rays' 1e-9 of jitter
+    decides). Every query on this scene runs the moving-geometry kernels, while the chain, and with
+    it the deep descent, is what it is in the static scene."""
+    return chain_scene(dev, CHAIN_WALL_MOTION)
+
+
+def chain_times(n=4096, seed=13):
+    """A time per chain ray: half of them (drawn at random, so not in step with the rays' kinds)
+    uniform in [0, 0.25), the rest uniform in (0.25, 1]; of every 16 the first is exactly 0, the
+    second exactly 0.25 and the third exactly 1."""
+    rng = np.random.default_rng(seed)
+    low = rng.random(n) < 0.5
+    t = np.where(low, rng.uniform(0.0, 0.25, n), 1.0 - rng.uniform(0.0, 0.75, n)).astype(F)
+    i = np.arange(n)
+    t[i % 16 == 0], t[i % 16 == 1], t[i % 16 == 2] = 0.0, 0.25, 1.0
+    assert t.min() == 0 and t.max() == 1 and not np.signbit(t).any()
+    return t
 
 
 # ----------------------------------------------------------------------------- refill rays
@@ -474,6 +532,194 @@ def node_plane_rays(qnodes, lo, hi):
     return np.array(org, F).reshape(-1, 4), np.array(dr, F).reshape(-1, 4)
 
 
+# ----------------------------------------------------------------------------- moving geometry: exact sweeps
+SWEEP_TIMES = (0.0, 0.25, 0.5, 0.75, 1.0)
+SWEEP_COPIES = 40
+(SW_QUAD_A, SW_QUAD_B, SW_ALONG, SW_COLLAPSE, SW_FLIP, SW_STATIC, SW_APPROACH, SW_APPROACH2, SW_STATIC2, SW_COVER_A,
+ SW_COVER_B, SW_COPIES) = range(12)  # global triangle ids; the copies are SW_COPIES .. SW_COPIES + 79
+
+
+def sweep_scene(dev):
+    """Small integer coordinates, motions that are multiples of 4 and times in SWEEP_TIMES: every
+    p + t * m and every product of the triangle test is exact. One case per band of y (10 apart),
+    so no case's rays meet another's triangles. Ng = cross(e1, e2) with e1 = p0 - p1, e2 = p2 - p0.
+    mesh 0 (ids 0, 1): exact_scene's quad (0,0,1) (4,0,1) (4,4,1) (0,4,1) as A (x >= y) and B,
+      moving by (8, 0, 0): it spans x in [8 t, 8 t + 4].
+    mesh 1 (id 2): (0,10,2) (4,10,2) (0,14,2) moving by (0, 0, 4), along the rays that go up: it
+      lies at z = 2 + 4 t.
+    mesh 2 (id 3): (0,20,1) (8,20,1) (0,28,1) whose third vertex moves by (0, -8, 0) onto the
+      first: half the size at 0.5, collapsed (Ng = 0, den == 0) at exactly 1.
+    mesh 3 (id 4), cullBackFaces: base (0,30,1) (8,30,1) moving by (0, 4, 0), apex (4,34,1) by
+      (0, -4, 0): the apex crosses the base at exactly 0.5 (collinear, den == 0); before, Ng =
+      (0, 0, -32 + 64 t) points down and the triangle is seen by rays going down, after, by rays
+      going up. (4, 32) lies inside it at every time but 0.5.
+    mesh 4 (id 5) static (0,40,1) (4,40,1) (0,44,1) and mesh 5 (id 6) the same at z = 3 moving by
+      (0, 0, -4): coincident at exactly 0.5 (the tie goes to id 5), the moving one behind the
+      static one before and in front of it after.
+    mesh 6 (id 7) moving and mesh 7 (id 8) static: the same pair at y + 10 with the ids the other
+      way round (the tie goes to the moving one).
+    mesh 8 (ids 9, 10): the quad at y + 60, z = 1, moving by (8, 0, 0), under
+    mesh 9 (ids 11 .. 90): 40 coincident static copies of the quad at y + 60, z = 2: the leaves of
+      exact_scene's copies, walked by the moving-geometry kernels."""
+    quad = np.array([[0, 0, 1], [4, 0, 1], [4, 4, 1], [0, 4, 1]], F)
+    two = np.array([[0, 1, 2], [0, 2, 3]], np.int32)
+    one = np.array([[0, 1, 2]], np.int32)
+
+    def tri(y, z):
+        return np.array([[0, y, z], [4, y, z], [0, y + 4, z]], F)
+
+    def mot(*rows):
+        return np.array(rows, F)
+
+    cq = quad + F([0, 60, 0])
+    copies = np.tile(quad + F([0, 60, 1]), (SWEEP_COPIES, 1))
+    cidx = np.concatenate([two + 4 * k for k in range(SWEEP_COPIES)])
+    meshes = [
+        (quad, two, False, None, mot(*[(8, 0, 0)] * 4)),
+        (tri(10, 2), one, False, None, mot(*[(0, 0, 4)] * 3)),
+        (np.array([[0, 20, 1], [8, 20, 1], [0, 28, 1]], F), one, False, None, mot((0, 0, 0), (0, 0, 0), (0, -8, 0))),
+        (np.array([[0, 30, 1], [8, 30, 1], [4, 34, 1]], F), one, True, None, mot((0, 4, 0), (0, 4, 0), (0, -4, 0))),
+        (tri(40, 1), one, False),
+        (tri(40, 3), one, False, None, mot(*[(0, 0, -4)] * 3)),
+        (tri(50, 3), one, False, None, mot(*[(0, 0, -4)] * 3)),
+        (tri(50, 1), one, False),
+        (cq, two, False, None, mot(*[(8, 0, 0)] * 4)),
+        (copies, cidx, False),
+    ]
+    return MeshScene(dev, meshes, eye=(4, 30, -40), look=(4, 30, 1))
+
+
+def sweep_rays():
+    """(org4, dir4, time, expected id, expected t, name) of the hand-written cases, each at the
+    five SWEEP_TIMES in adjacent slots (so one wave holds the five times of a ray). Expected id -1:
+    no triangle accepted; expected t is checked for hits."""
+    up, dn = (0, 0, 1), (0, 0, -1)
+    M = -1
+    rows = []
+
+    def add(name, ray, tris, ts=1.0):
+        ts = [ts] * 5 if np.isscalar(ts) else ts
+        assert len(tris) == 5 and len(ts) == 5
+        for k, time in enumerate(SWEEP_TIMES):
+            rows.append((f"{name} @ {time}", ray, time, tris[k], ts[k]))
+
+    # the translated quad under (6, 1): not there yet, its edge x = 4 (A), A's interior, its edge
+    # x = 0 (B), gone; under (6, 3) the interior is B's
+    add("quad passes 6,1", _ray((6, 1, 0), up), [M, SW_QUAD_A, SW_QUAD_A, SW_QUAD_B, M])
+    add("quad passes 6,3", _ray((6, 3, 0), up), [M, SW_QUAD_A, SW_QUAD_B, SW_QUAD_B, M])
+    add("quad passes 6,1 from above", _ray((6, 1, 2), dn), [M, SW_QUAD_A, SW_QUAD_A, SW_QUAD_B, M])
+    # its vertices (4, 0) and (0, 0) and the end of its diagonal pass (6, 0) and (6, 4)
+    add("quad passes 6,0", _ray((6, 0, 0), up), [M, SW_QUAD_A, SW_QUAD_A, SW_QUAD_A, M])
+    add("quad passes 6,4", _ray((6, 4, 0), up), [M, SW_QUAD_A, SW_QUAD_B, SW_QUAD_B, M])
+    # the triangle moving along the ray: t = 2 + 4 time against tfar and tnear
+    far = [2.0, 3.0, 4.0, 5.0, 6.0]
+    add("along the ray", _ray((1, 11, 0), up), [SW_ALONG] * 5, far)
+    add("along the ray, tfar 4", _ray((1, 11, 0), up, 0.0, 4.0), [SW_ALONG, SW_ALONG, M, M, M], far)
+    add("along the ray, tnear 3", _ray((1, 11, 0), up, 3.0), [M, M, SW_ALONG, SW_ALONG, SW_ALONG], far)
+    add("along the ray, tnear 2, tfar 6", _ray((1, 11, 0), up, 2.0, 6.0), [M, SW_ALONG, SW_ALONG, SW_ALONG, M], far)
+    # against its motion, from above: t = 8 - (2 + 4 time)
+    add("against the ray, tfar 4", _ray((1, 11, 8), dn, 0.0, 4.0), [M, M, M, SW_ALONG, SW_ALONG], [6.0, 5.0, 4.0, 3.0, 2.0])
+    # the collapsing triangle: (1, 26) leaves it before 0.25, (1, 21) stays inside until it is
+    # gone at 1; (0, 26) on the edge x = 0 that shrinks to y <= 26 at exactly 0.25
+    add("collapse 1,26", _ray((1, 26, 0), up), [SW_COLLAPSE, M, M, M, M])
+    add("collapse 1,21", _ray((1, 21, 0), up), [SW_COLLAPSE] * 4 + [M])
+    add("collapse 0,26", _ray((0, 26, 0), up), [SW_COLLAPSE, SW_COLLAPSE, M, M, M])
+    add("collapse 1,21 from above", _ray((1, 21, 2), dn), [SW_COLLAPSE] * 4 + [M])
+    # the culled triangle that turns over, from below and from above
+    add("flip from below", _ray((4, 32, 0), up), [M, M, M, SW_FLIP, SW_FLIP])
+    add("flip from above", _ray((4, 32, 2), dn), [SW_FLIP, SW_FLIP, M, M, M])
+    add("flip from below 3,32", _ray((3, 32, 0), up), [M, M, M, SW_FLIP, SW_FLIP])
+    add("flip from above 5,32", _ray((5, 32, 2), dn), [SW_FLIP, SW_FLIP, M, M, M])
+    # coincident at 0.5 only: from z = -2 the static one lies at 3, the moving one at 5 - 4 time
+    meet_id = [SW_STATIC, SW_STATIC, SW_STATIC, SW_APPROACH, SW_APPROACH]
+    meet_id2 = [SW_STATIC2, SW_STATIC2, SW_APPROACH2, SW_APPROACH2, SW_APPROACH2]
+    meet_t = [3.0, 3.0, 3.0, 2.0, 1.0]
+    add("meet, static id first", _ray((1, 41, -2), up), meet_id, meet_t)
+    add("meet, moving id first", _ray((1, 51, -2), up), meet_id2, meet_t)
+    # from above (z = 4): the static one at 3, the moving one at 1 + 4 time
+    add("meet from above, static id first", _ray((1, 41, 4), dn), [SW_APPROACH, SW_APPROACH, SW_STATIC, SW_STATIC, SW_STATIC],
+        [1.0, 2.0, 3.0, 3.0, 3.0])
+    add("meet from above, moving id first", _ray((1, 51, 4), dn),
+        [SW_APPROACH2, SW_APPROACH2, SW_APPROACH2, SW_STATIC2, SW_STATIC2], [1.0, 2.0, 3.0, 3.0, 3.0])
+    # on the edge y = 40 and the vertex (0, 40) the two coincide in
+    add("meet on an edge", _ray((2, 40, -2), up), meet_id, meet_t)
+    add("meet on a vertex", _ray((0, 50, -2), up), meet_id2, meet_t)
+    # under the copies: the moving quad covers (x, y) while x lies in [8 t, 8 t + 4]; then the ray
+    # goes on into the 40 ties, of which the smallest id wins
+    A, B = SW_COPIES, SW_COPIES + 1
+    for x, y in ((3.5, 60.5), (0.5, 63.5), (3.5, 62.5), (1.5, 63.0), (2.0, 62.0), (3.0, 60.0), (0.5, 60.5)):
+        a = x >= y - 60
+        cover = [SW_COVER_A if (x - 8 * t) >= y - 60 else SW_COVER_B for t in SWEEP_TIMES]
+        under = [8 * t <= x <= 8 * t + 4 for t in SWEEP_TIMES]
+        assert any(under) and not all(under)
+        add(f"copies {x},{y}", _ray((x, y, 0), up), [c if u else (A if a else B) for c, u in zip(cover, under)],
+            [1.0 if u else 2.0 for u in under])
+    r = np.array([x[1] for x in rows], F)
+    return (np.ascontiguousarray(r[:, :4]), np.ascontiguousarray(r[:, 4:]), np.array([x[2] for x in rows], F),
+            np.array([x[3] for x in rows], np.int32), np.array([x[4] for x in rows], F), [x[0] for x in rows])
+
+
+# ----------------------------------------------------------------------------- moving geometry: a field
+# The first field's per-vertex motions are uniform in [-FIELD_MOTION, FIELD_MOTION]^3. With 1 a stale time (the
+# previous ray's) changes the occlusion flag of 1.6 % of the base rays only (the field stays one connected sheet: a
+# ray aimed at it still meets a neighbour), with 4 of 3.8 %, with 8 of 5.3 %: the smallest of these that meets
+# test_trace_motion's bar of 1/20. The closest hit changes for 34.5 %, 38.9 % and 43.3 %.
+FIELD_MOTION = 8.0
+FIELD_EYE, FIELD_LOOK = (12.0, 12.0, -6.0), (14.0, 0.0, 8.0)
+
+
+def moving_field_scene(dev, light=2.0):
+    """refit_meshes()' two height fields before REFIT_SCALE (the same seed and draws): the 23 x 17
+    field (782 triangles, vertex normals) with per-vertex motions uniform in [-FIELD_MOTION,
+    FIELD_MOTION]^3, the 9 x 31 field (558 triangles) static. Neighbouring vertices move apart and
+    towards each other, so a triangle's shape, facing and box change over the frame, and the sheet
+    folds over itself."""
+    rng = np.random.default_rng(23)
+    g0, i0, n0 = height_field(23, 17, (0, 0, 0), rng, normals=True)
+    g1, i1, _ = height_field(9, 31, (30, 0, -6), rng)
+    mot = np.random.default_rng(31).uniform(-FIELD_MOTION, FIELD_MOTION, g0.shape).astype(F) + F(0)
+    return MeshScene(dev, [(g0, i0, False, n0, mot), (g1, i1, False)], eye=FIELD_EYE, look=FIELD_LOOK, light=light)
+
+
+def moving_field_rays(S, n=1 << 16, seed=37):
+    """(org4, dir4 with tfar inf, time, far) for moving_field_scene: times uniform in [0, 1], of
+    every 16 the first exactly 0 and the second exactly 1; three quarters of the rays (index % 4
+    != 3) aimed from 10 to 30 away at where a random triangle's centroid is at the ray's own
+    time, jittered by 0.3, the rest from inside the scene's bounds in a random direction. far: 0.5
+    to 1.5 times the distance to the aim (5 for the random rays), for cut-short variants."""
+    rng = np.random.default_rng(seed)
+    i = np.arange(n)
+    time = rng.uniform(0.0, 1.0, n).astype(F)
+    time[i % 16 == 0], time[i % 16 == 1] = 0.0, 1.0
+    org = np.zeros((n, 4), F)
+    dr = np.zeros((n, 4), F)
+    dr[:, 3] = INF
+    far = np.full(n, 5.0)
+    m = np.flatnonzero(i % 4 != 3)
+    tri = rng.integers(0, len(S.tri9), len(m))
+    p = S.tri9[tri].astype(np.float64) + time[m, None].astype(np.float64) * S.mot9[tri].astype(np.float64)
+    aim = p.reshape(-1, 3, 3).mean(1) + rng.uniform(-0.3, 0.3, (len(m), 3))
+    v = rng.normal(size=(len(m), 3))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    dist = rng.uniform(10, 30, len(m))
+    org[m, :3] = aim + v * dist[:, None]
+    dr[m, :3] = -v
+    far[m] = dist * rng.uniform(0.5, 1.5, len(m))
+    m = np.flatnonzero(i % 4 == 3)
+    org[m, :3] = rng.uniform(S.info["bboxLo"], S.info["bboxHi"], (len(m), 3))
+    v = rng.normal(size=(len(m), 3))
+    dr[m, :3] = v / np.linalg.norm(v, axis=1, keepdims=True)
+    return org, dr, time, far.astype(F)
+
+
+def moving_field_base(S):
+    """The base set of the moving-field tests: moving_field_rays through refill_base (void and
+    cheap rays mixed in). Returns (org4, dir4, time)."""
+    org, dr, time, _ = moving_field_rays(S)
+    org, dr = refill_base(org, dr, S.info["bboxLo"], S.info["bboxHi"])
+    return org, dr, time
+
+
 # ----------------------------------------------------------------------------- ray queries on the device
 SENT_F = np.float32(-12345.0)
 SENT_I = 0x5A5A5A5A
@@ -487,18 +733,24 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def query(dev, scene, org, dr, n=None, guard=64):
+def query(dev, scene, org, dr, n=None, guard=64, time=None):
     """yrtIntersect and yrtOccluded on the first n rays into sentinel-filled outputs with `guard`
-    spare elements: every slot < n written, the guard untouched. Returns (hit (n, 4), occ (n,))."""
+    spare elements: every slot < n written, the guard untouched. Returns (hit (n, 4), occ (n,)).
+    time (one float per ray): the timed calls, yrtIntersectTimed and yrtOccludedTimed."""
     import torch
     n = len(org) if n is None else n
     o = torch.from_numpy(np.array(org[:max(n, 1)], np.float32)).cuda()
     d = torch.from_numpy(np.array(dr[:max(n, 1)], np.float32)).cuda()
     hit = torch.full((n + guard, 4), float(SENT_F), dtype=torch.float32, device="cuda")
     occ = torch.full((n + guard,), SENT_I, dtype=torch.int32, device="cuda")
+    tp = None
+    if time is not None:
+        assert len(time) >= n
+        t = torch.from_numpy(np.array(time[:max(n, 1)], np.float32)).cuda()
+        tp = t.data_ptr()
     torch.cuda.synchronize()
-    dev.intersect(scene, o.data_ptr(), d.data_ptr(), n, hit.data_ptr())
-    dev.occluded(scene, o.data_ptr(), d.data_ptr(), n, occ.data_ptr())
+    dev.intersect(scene, o.data_ptr(), d.data_ptr(), n, hit.data_ptr(), time_ptr=tp)
+    dev.occluded(scene, o.data_ptr(), d.data_ptr(), n, occ.data_ptr(), time_ptr=tp)
     h, c = hit.cpu().numpy(), occ.cpu().numpy()
     assert (h[n:] == SENT_F).all() and (c[n:] == SENT_I).all(), "guard region written"
     assert (ids(h[:n]) != ids(np.full((1, 4), SENT_F))[0]).all() and (c[:n] != SENT_I).all(), "slot not written"

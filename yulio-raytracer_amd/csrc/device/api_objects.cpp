@@ -619,21 +619,29 @@ int yrtSetStopFlag(YRTDevice dev, YRTHandle renderer, volatile int* flag) {
   DEV_END(-1)
 }
 
-int yrtIntersect(YRTDevice dev, YRTHandle scene, const float* org4, const float* dir4, uint32_t n, float* hit4,
-                 void* stream) {
+int yrtIntersectTimed(YRTDevice dev, YRTHandle scene, const float* org4, const float* dir4, const float* time,
+                      uint32_t n, float* hit4, void* stream) {
   DEV_GUARD(dev, -1)
   auto S = dev->d->get<SceneObj>(scene, "scene");
-  dev->d->intersect(*S, org4, dir4, n, hit4, nullptr, stream ? (hipStream_t)stream : dev->d->stream);
+  dev->d->intersect(*S, org4, dir4, time, n, hit4, nullptr, stream ? (hipStream_t)stream : dev->d->stream);
   return 0;
   DEV_END(-1)
 }
-int yrtOccluded(YRTDevice dev, YRTHandle scene, const float* org4, const float* dir4, uint32_t n, int32_t* occ,
-                void* stream) {
+int yrtOccludedTimed(YRTDevice dev, YRTHandle scene, const float* org4, const float* dir4, const float* time,
+                     uint32_t n, int32_t* occ, void* stream) {
   DEV_GUARD(dev, -1)
   auto S = dev->d->get<SceneObj>(scene, "scene");
-  dev->d->intersect(*S, org4, dir4, n, nullptr, occ, stream ? (hipStream_t)stream : dev->d->stream);
+  dev->d->intersect(*S, org4, dir4, time, n, nullptr, occ, stream ? (hipStream_t)stream : dev->d->stream);
   return 0;
   DEV_END(-1)
+}
+int yrtIntersect(YRTDevice dev, YRTHandle scene, const float* org4, const float* dir4, uint32_t n, float* hit4,
+                 void* stream) {
+  return yrtIntersectTimed(dev, scene, org4, dir4, nullptr, n, hit4, stream);
+}
+int yrtOccluded(YRTDevice dev, YRTHandle scene, const float* org4, const float* dir4, uint32_t n, int32_t* occ,
+                void* stream) {
+  return yrtOccludedTimed(dev, scene, org4, dir4, nullptr, n, occ, stream);
 }
 int yrtTriangleIds(YRTDevice dev, YRTHandle scene, int32_t tri, int32_t* geomID, int32_t* primID) {
   DEV_GUARD(dev, -1)

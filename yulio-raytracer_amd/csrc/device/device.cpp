@@ -104,20 +104,25 @@ void fb_read_back(FrameBufferObj& F, int id) {
 }
 
 // ---------------------------------------------------------------- ray queries
-void Device::intersect(SceneObj& S, const float* org4, const float* dir4, uint32_t n, float* hit4, int32_t* occ,
-                       hipStream_t st) {
+void Device::intersect(SceneObj& S, const float* org4, const float* dir4, const float* time, uint32_t n, float* hit4,
+                       int32_t* occ, hipStream_t st) {
+  if (!gpu) throw std::runtime_error("ray query: host-only device (created with parms \"host\")");
   HIP_CHECK(hipSetDevice(hipDevice));
   if (!S.gpu) throw std::runtime_error("scene not committed");
+  // a static scene has no triMotion records and ignores the rays' times (Ray::time is not read by
+  // a static mesh): the static kernels run, and `time` is never dereferenced
+  if (!S.gpu->hasMotion) time = nullptr;
   GpuCtx& g = *ctx[0];
   g.dCount.alloc(sizeof(unsigned));
   HIP_CHECK(hipMemcpyAsync(g.dCount.p, &n, sizeof(unsigned), hipMemcpyHostToDevice, st));
   SceneView sv = S.gpu->view;
   sv.traceSpill = spill();
   if (occ)
-    launch_trace_any(sv, (const float4*)org4, (const float4*)dir4, g.dCount.as<unsigned>(), 1, (int)n, occ, st);
+    launch_trace_any(sv, (const float4*)org4, (const float4*)dir4, g.dCount.as<unsigned>(), 1, (int)n, occ, st, nullptr,
+                     time);
   else
     launch_trace_closest(sv, (const float4*)org4, (const float4*)dir4, g.dCount.as<unsigned>(), 1, (int)n,
-                         (float4*)hit4, st);
+                         (float4*)hit4, st, time);
   HIP_CHECK(hipStreamSynchronize(st));
 }
 

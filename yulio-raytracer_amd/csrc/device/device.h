@@ -376,8 +376,10 @@ class Device {
   // A render call that fails before reaching render() (bad handles, host-only device) still
   // joins the status exchange with flag 0, so the peers fail instead of waiting for it.
   void fail_proc_gather();
-  void intersect(SceneObj& S, const float* org4, const float* dir4, uint32_t n, float* hit4, int32_t* occ,
-                 hipStream_t st);
+  // yrtIntersect / yrtOccluded (occ set: any hit); time: one float per ray or null (the untimed
+  // call), ignored by a scene without moving geometry
+  void intersect(SceneObj& S, const float* org4, const float* dir4, const float* time, uint32_t n, float* hit4,
+                 int32_t* occ, hipStream_t st);
   // the first-hit guide frames of the W x H views of C (one frame: one camera) as [face][H][W]
   // arrays in ctx[0]'s dGuidePos / dGuideNrm (enqueued on the primary stream); albedo: the same
   // pass also fills dGuideAlbedo (k_guides<true>). Checks the scene and the pixel count.

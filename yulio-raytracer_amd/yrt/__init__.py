@@ -463,11 +463,21 @@ class Device:
         return a
 
     # -- hot-path ray queries (device pointers: e.g. torch.cuda tensors' data_ptr())
-    def intersect(self, scene, org4_ptr, dir4_ptr, n, hit4_ptr, stream=None):
-        self._rc(N.dev.yrtIntersect(self.h, scene, org4_ptr, dir4_ptr, n, hit4_ptr, stream), "rtcIntersect")
+    # time_ptr: n floats, one Ray::time in [0, 1] per ray (yrtIntersectTimed / yrtOccludedTimed);
+    # None is the untimed call, which on a moving scene is time 0
+    def intersect(self, scene, org4_ptr, dir4_ptr, n, hit4_ptr, stream=None, time_ptr=None):
+        if time_ptr is None:
+            rc = N.dev.yrtIntersect(self.h, scene, org4_ptr, dir4_ptr, n, hit4_ptr, stream)
+        else:
+            rc = N.dev.yrtIntersectTimed(self.h, scene, org4_ptr, dir4_ptr, time_ptr, n, hit4_ptr, stream)
+        self._rc(rc, "rtcIntersect")
 
-    def occluded(self, scene, org4_ptr, dir4_ptr, n, occ_ptr, stream=None):
-        self._rc(N.dev.yrtOccluded(self.h, scene, org4_ptr, dir4_ptr, n, occ_ptr, stream), "rtcOccluded")
+    def occluded(self, scene, org4_ptr, dir4_ptr, n, occ_ptr, stream=None, time_ptr=None):
+        if time_ptr is None:
+            rc = N.dev.yrtOccluded(self.h, scene, org4_ptr, dir4_ptr, n, occ_ptr, stream)
+        else:
+            rc = N.dev.yrtOccludedTimed(self.h, scene, org4_ptr, dir4_ptr, time_ptr, n, occ_ptr, stream)
+        self._rc(rc, "rtcOccluded")
 
     def triangle_ids(self, scene, tri):
         g, p = C.c_int32(), C.c_int32()

@@ -148,7 +148,9 @@ _sig(dev, "yrtSetStatusCallback", i32, vp, vp, STATUS_CB, vp)
 _sig(dev, "yrtSetStopFlag", i32, vp, vp, C.POINTER(C.c_int))
 _sig(dev, "yrtIntersect", i32, vp, vp, vp, vp, C.c_uint32, vp, vp)
 _sig(dev, "yrtOccluded", i32, vp, vp, vp, vp, C.c_uint32, vp, vp)
-_sig(dev, "yrtTriangleIds", i32, vp, vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+_sig(dev, "yrtIntersectTimed", i32, vp, vp, vp, vp, vp, C.c_uint32, vp, vp)
+_sig(dev, "yrtOccludedTimed", i32, vp, vp, vp, vp, vp, C.c_uint32, vp, vp)
+_sig(dev, "yrtTriangleIds",i32, vp, vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 _sig(dev, "yrtGetRenderStats", i32, vp, C.POINTER(RenderStats))
 _sig(dev, "yrtSetKernelTiming", i32, vp, i32)
 _sig(dev, "yrtSetLanes", i32, vp, i32)
