@@ -134,6 +134,56 @@ YRT_API int yrtSwapBuffers(YRTDevice dev, YRTHandle framebuffer);
  * the camera ray through image-plane point (x, y) in [0,1]^2. Returns 1 hit, 0 miss, <0 error. */
 YRT_API int yrtPick(YRTDevice dev, YRTHandle camera, float x, float y, YRTHandle scene, float* px, float* py,
                     float* pz);
+/* ---- adaptive sampling: converged 16x16 tiles stop, only the active ones render ----
+ * yrtRenderAdaptive renders one frame in progressive iterations of the renderer's committed spp
+ * each. It starts like accumulate = 0 (the renderer's iteration is reset, the framebuffer's sums
+ * start from this frame); iteration k = 0, 1, ... renders the active tiles with sampler iteration k
+ * and adds them into the framebuffer's sums exactly as yrtRenderFrame(..., 1) does, and the even
+ * iterations also into a second buffer of the framebuffer, the half buffer. After iteration k,
+ * when n = k + 1 is even and n >= minIterations (raised to the next even number, at least 2), the
+ * error estimate E_T of every active tile is computed from the two buffers (Dammertz et al. 2010,
+ * csrc/common/yrt_tile_error.h; linear radiance, the tone mapper plays no part) and a tile stops
+ * iff E_T < threshold (strict; a NaN never stops). A stopped tile is never touched again and keeps
+ * the display of its last iteration, so its pixels are, bit for bit, those of n calls of
+ * yrtRenderFrame(..., 1). The call ends when no tile is active, at n = maxIterations, or when the
+ * renderer's stop flag is set between iterations. threshold <= 0 stops nothing: the call equals
+ * maxIterations progressive frames. Afterwards the renderer's iteration is n, and
+ * yrtRenderFrame(..., accumulate = 1) into the framebuffer is refused until a frame with
+ * accumulate = 0 has been rendered into it.
+ * Refused with an error and no launch: the debug renderer, a device with more than one render
+ * context (devices=...), an armed tile shard, communicator or hub, armed ray capture,
+ * maxIterations < 1 and a non-finite threshold.
+ * size = sizeof of the caller's struct, as in YRTDenoiseParams: a shorter params struct is read up
+ * to its size, the remaining fields take their defaults (0.05, 2, 64; yrtAdaptiveDefaults), and
+ * the stats are written up to the caller's size. out may be NULL. */
+typedef struct YRTAdaptiveParams {
+  uint32_t size;
+  float threshold;
+  int minIterations, maxIterations;
+} YRTAdaptiveParams;
+/* iterations: n. tiles: the frame's tiles; tilesStopped: those the check stopped. samples: the sum
+ * of the pixel weights (samples traced inside the image). msTotal: the call; msError: its checks
+ * (estimate, compaction and the read of the new tile count), host clock. */
+typedef struct YRTAdaptiveStats {
+  uint32_t size;
+  int32_t iterations;
+  int64_t tiles, tilesStopped;
+  double samples, msTotal, msError;
+} YRTAdaptiveStats;
+YRT_API int yrtAdaptiveDefaults(YRTAdaptiveParams* p);
+YRT_API int yrtRenderAdaptive(YRTDevice dev, YRTHandle renderer, YRTHandle camera, YRTHandle scene,
+                              YRTHandle tonemapper, YRTHandle framebuffer, const YRTAdaptiveParams* p,
+                              YRTAdaptiveStats* out);
+/* The tiles of the framebuffer's last adaptive render in image tile order, row-major: returns
+ * their number (0: none yet, -1: error) and fills, for the first numTiles of them, the iterations
+ * each ran and its last computed E_T (+inf for a tile no check looked at). Either array may be NULL. */
+YRT_API int yrtGetAdaptiveTiles(YRTDevice dev, YRTHandle framebuffer, int32_t* iterations, float* error,
+                                size_t numTiles);
+/* Host-side: E_T of every tile of a width x height frame from its sums accu4 and half sums half4
+ * ([height][width][4] floats: r, g, b, weight), by the header the kernel compiles;
+ * errorPerTile holds ceil(width / 16) * ceil(height / 16) floats. -1 on a null pointer or an
+ * empty frame. */
+YRT_API int yrtDebugTileError(const float* accu4, const float* half4, int width, int height, float* errorPerTile);
 /* ---- denoise: first-hit guide buffers and an edge-avoiding a-trous filter ---- */
 /* yrtRenderGuides: for pixel (x, y) of a width x height view, rtPick's camera ray through the
  * image-plane point ((x + .5) / width, (y + .5) / height) (time 0 in moving scenes):

@@ -4,6 +4,7 @@
 #include <strings.h>
 
 #include "../common/yrt_cube_tap.h"
+#include "../common/yrt_tile_error.h"
 #include "../common/yrt_tile_scatter.h"
 #include "device.h"
 #include "image_io.h"
@@ -594,6 +595,76 @@ int yrtGetSceneRefits(YRTDevice dev, YRTHandle scene) {
   if (!S || !S->gpu) throw std::runtime_error("scene not committed");
   return S->gpu->refits;
   DEV_END(-1)
+}
+
+// The library's YRTAdaptiveParams: the defaults overlaid by the fields the caller's struct holds
+// (the convention of YRTDenoiseParams). The values are judged by Device::render_adaptive.
+static YRTAdaptiveParams adaptive_params(const YRTAdaptiveParams* p) {
+  YRTAdaptiveParams d;
+  d.size = (uint32_t)sizeof(YRTAdaptiveParams);
+  d.threshold = 0.05f;
+  d.minIterations = 2;
+  d.maxIterations = 64;
+  if (!p) return d;
+  if (p->size < sizeof(uint32_t)) throw std::runtime_error("YRTAdaptiveParams: size is smaller than the size field");
+  const size_t n = p->size;
+#define YRT_AD_FIELD(f) \
+  if (n >= offsetof(YRTAdaptiveParams, f) + sizeof(d.f)) d.f = p->f
+  YRT_AD_FIELD(threshold);
+  YRT_AD_FIELD(minIterations);
+  YRT_AD_FIELD(maxIterations);
+#undef YRT_AD_FIELD
+  return d;
+}
+
+int yrtAdaptiveDefaults(YRTAdaptiveParams* p) {
+  if (!p || p->size < sizeof(uint32_t)) return -1;
+  const YRTAdaptiveParams d = adaptive_params(nullptr);
+  memcpy((char*)p + sizeof(uint32_t), (const char*)&d + sizeof(uint32_t),
+         std::min<size_t>(p->size, sizeof(d)) - sizeof(uint32_t));
+  return 0;
+}
+
+int yrtRenderAdaptive(YRTDevice dev, YRTHandle renderer, YRTHandle camera, YRTHandle scene, YRTHandle tonemapper,
+                      YRTHandle framebuffer, const YRTAdaptiveParams* p, YRTAdaptiveStats* out) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  auto R = D.get<RendererObj>(renderer, "renderer");
+  auto C = D.get<CameraObj>(camera, "camera");
+  auto S = D.get<SceneObj>(scene, "scene");
+  auto T = D.get<ToneMapperObj>(tonemapper, "tonemapper");
+  auto F = D.get<FrameBufferObj>(framebuffer, "framebuffer");
+  if (!R || !C || !S || !T || !F) throw std::runtime_error("rtRenderAdaptive: null handle");
+  if (out && out->size < sizeof(uint32_t)) throw std::runtime_error("YRTAdaptiveStats: size not set");
+  YRTAdaptiveStats r;
+  memset(&r, 0, sizeof(r));
+  D.render_adaptive(*R, *C, *S, *T, *F, adaptive_params(p), r);
+  if (out) {
+    r.size = out->size;
+    memcpy(out, &r, std::min((size_t)out->size, sizeof(r)));  // never past the caller's struct
+  }
+  return 0;
+  DEV_END(-1)
+}
+
+int yrtGetAdaptiveTiles(YRTDevice dev, YRTHandle framebuffer, int32_t* iterations, float* error, size_t numTiles) {
+  DEV_GUARD(dev, -1)
+  auto F = dev->d->get<FrameBufferObj>(framebuffer, "framebuffer");
+  if (!F) throw std::runtime_error("yrtGetAdaptiveTiles: null handle");
+  const size_t n = std::min(numTiles, F->tileIterations.size());
+  if (iterations && n) memcpy(iterations, F->tileIterations.data(), n * sizeof(int32_t));
+  if (error && n) memcpy(error, F->tileError.data(), n * sizeof(float));
+  return (int)F->tileIterations.size();
+  DEV_END(-1)
+}
+
+int yrtDebugTileError(const float* accu4, const float* half4, int width, int height, float* errorPerTile) {
+  if (!accu4 || !half4 || !errorPerTile || width < 1 || height < 1) return -1;
+  const int tilesX = (width + 15) / 16, tilesY = (height + 15) / 16;
+  for (int ty = 0; ty < tilesY; ++ty)
+    for (int tx = 0; tx < tilesX; ++tx)
+      errorPerTile[(size_t)ty * tilesX + tx] = yrt_tile_error(accu4, half4, width, height, tx, ty);
+  return 0;
 }
 
 }  // extern "C"

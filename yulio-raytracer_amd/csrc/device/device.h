@@ -3,6 +3,7 @@
 //   device.cpp         Device's ray queries, frame read-back, scene commit
 //   render.cpp         Device::render (the frame job), Device::render_shard (one device's share)
 //   render_job.{h,cpp} the batch plan and the wavefront lane scheduler render_shard runs
+//   adaptive.cpp       Device::render_adaptive (progressive iterations over the tiles not yet converged)
 //   denoise.cpp        Device::guides, Device::denoise (a frame or a cube's faces), the cube-camera check
 //   gather_device.cpp  Device::gather_local, Device::gather_process
 //   api_objects.cpp, api_tools.cpp  the extern "C" entry points (include/yrt_device.h)
@@ -349,14 +350,32 @@ class Device {
               const std::vector<FrameBufferObj*>& F, int accumulate);
   // makes ctx[0]->blk a frame block no framebuffer holds unread frames in
   void rotate_frame_block();
+  // the W x H frames a job rendered into ctx[0]->blk, frame k to F[k]: each framebuffer keeps a
+  // reference to its frame in HBM (FrameBufferObj::Pending) or, with user pixels, reads it back now
+  void hand_over_frames(const std::vector<FrameBufferObj*>& F, int W, int H);
   // F's accumulation buffer on g, created cleared (enqueued on g's stream) at g's first frame
   // into F; later frames only look it up
   static float4* frame_accu(FrameBufferObj& F, GpuCtx& g);
   // Renders the tiles of shard (index, count) of the frame into g's full-size buffers (the other
   // tiles' pixels are left zero when count > 1). accu: the framebuffer's accumulation buffer on g
   // (frame_accu) of a one-frame job, null for a multi-frame job or the debug renderer.
+  // pass: one iteration of an adaptive render, the listed tiles of the whole frame (index 0, count 1).
+  struct AdaptivePass {
+    const int* tileList;  // device array: the active image tiles, ascending
+    int count;
+    float4* half;         // the half buffer this iteration is also added into, or null
+  };
   void render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vector<CameraObj*>& C, ToneMapperObj& T,
-                    int W, int H, int index, int count, int accumulate, bool reportProgress, float4* accu);
+                    int W, int H, int index, int count, int accumulate, bool reportProgress, float4* accu,
+                    const AdaptivePass* pass = nullptr);
+  // yrtRenderAdaptive (adaptive.cpp): one frame in progressive iterations of R.spp samples, each
+  // over the tiles whose error estimate (common/yrt_tile_error.h) has not fallen below p.threshold
+  void render_adaptive(RendererObj& R, CameraObj& C, SceneObj& S, ToneMapperObj& T, FrameBufferObj& F,
+                       const YRTAdaptiveParams& p, YRTAdaptiveStats& out);
+  // F's half buffer on g (FrameBufferObj::Adaptive), allocated at g's first adaptive render into F
+  static float4* frame_half(FrameBufferObj& F, GpuCtx& g);
+  // device scratch of the adaptive check: two tile lists, stop flags, the records, the count word
+  DevBuf dTileList[2], dTileStopped, dTileError, dTileIterations, dTileCount;
   int gather_local(const SlabLayout& base, int numTiles);
   // the render's output is this shard alone (no gather fills the other shards' tiles): those
   // pixels must read as zeros, so per-shard images compose by sum

@@ -243,6 +243,21 @@ struct FrameBufferObj : Object {
   // the last frame came from a multi-frame job (rtRenderFrames), which keeps no per-framebuffer
   // sums: rtRenderFrame(..., accumulate=1) is refused until a frame with accumulate=0
   bool accuFromJob = false;
+  // Adaptive renders (yrtRenderAdaptive, adaptive.cpp) keep, beside the sums, the half buffer (the
+  // sums of the even iterations, shaped as Accu::sums) and the tile records of the last adaptive
+  // render, per GPU context; created cleared on first use and released with the framebuffer.
+  struct Adaptive {
+    uint64_t ctxSerial = 0;
+    DevBuf half;  // float4 [height][width]
+  };
+  std::vector<std::unique_ptr<Adaptive>> adaptive;
+  // the last adaptive render's tiles in image tile order (yrtGetAdaptiveTiles): iterations run and
+  // the last computed E_T (+inf: never checked); empty: no adaptive render yet
+  std::vector<int32_t> tileIterations;
+  std::vector<float> tileError;
+  // the last frame came from an adaptive render, whose tiles hold different numbers of iterations:
+  // rtRenderFrame(..., accumulate=1) is refused until a frame with accumulate=0
+  bool accuFromAdaptive = false;
   // A frame still on the device (per buffer id): rtRenderFrame leaves it in HBM and
   // rtMapFrameBuffer copies it to the host pixels on first access (fb_read_back, device.cpp).
   struct Pending {

@@ -101,6 +101,11 @@ void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& 
     if (accumulate && nf == 1 && !R.debug && F[0]->accuFromJob)
       throw std::runtime_error("rtRenderFrame: accumulate=1 on a framebuffer whose last frame came from a multi-frame "
                                "job (rtRenderFrames keeps no accumulation): render it with accumulate=0 first");
+    // an adaptive render leaves tiles of different iteration counts: no later frame continues them
+    if (accumulate && nf == 1 && !R.debug && F[0]->accuFromAdaptive)
+      throw std::runtime_error("rtRenderFrame: accumulate=1 on a framebuffer whose last frame came from an adaptive "
+                               "render (rtRenderAdaptive stops tiles at different iterations): render it with "
+                               "accumulate=0 first");
     if (!accumulate) R.iteration = 0;
     rotate_frame_block();
     std::vector<GpuScene*> scenes(nr);
@@ -148,7 +153,10 @@ void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& 
   if (!localErr.empty()) throw std::runtime_error(localErr);
   R.iteration++;
   if (!R.debug)
-    for (FrameBufferObj* f : F) f->accuFromJob = nf > 1;
+    for (FrameBufferObj* f : F) {
+      f->accuFromJob = nf > 1;
+      f->accuFromAdaptive = false;
+    }
   for (int k = 0; k < nr; ++k) {
     const YRTRenderStats& s = ctx[k]->stats;
     stats.raysClosest += s.raysClosest;
@@ -166,9 +174,21 @@ void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& 
   // host pixels keeps a reference to the frame in HBM instead, read back by rtMapFrameBuffer
   // (the reference's only access to the pixels, singleray_device.cpp:439-447): frames nobody
   // maps cross no PCIe.
+  if (!(procGather && shardIndex != 0)) hand_over_frames(F, W, H);
+  stats.samples = ctx[0]->stats.samples;
+  stats.gather = gatherPath;
+  const auto tEnd = std::chrono::steady_clock::now();
+  if (tRendered == t0) tRendered = tEnd;  // the render threw before its end (collective error path)
+  stats.msTotal = std::chrono::duration<double, std::milli>(tEnd - t0).count();
+  stats.msRender = std::chrono::duration<double, std::milli>(tRendered - t0).count();
+  stats.msGather = std::chrono::duration<double, std::milli>(tEnd - tRendered).count();
+  status(R, 2, 1.f);
+}
+
+void Device::hand_over_frames(const std::vector<FrameBufferObj*>& F, int W, int H) {
   GpuCtx& g0 = *ctx[0];
   HIP_CHECK(hipSetDevice(g0.hipDevice));
-  for (int k = 0; k < nf && !(procGather && shardIndex != 0); ++k) {
+  for (int k = 0; k < (int)F.size(); ++k) {
     FrameBufferObj& Fk = *F[k];
     FrameBufferObj::Pending pf;
     pf.keep = g0.blk;
@@ -179,14 +199,6 @@ void Device::render(RendererObj& R, const std::vector<CameraObj*>& C, SceneObj& 
     Fk.pending[Fk.cur] = pf;
     if (!Fk.userPtrs.empty()) fb_read_back(Fk, Fk.cur);
   }
-  stats.samples = ctx[0]->stats.samples;
-  stats.gather = gatherPath;
-  const auto tEnd = std::chrono::steady_clock::now();
-  if (tRendered == t0) tRendered = tEnd;  // the render threw before its end (collective error path)
-  stats.msTotal = std::chrono::duration<double, std::milli>(tEnd - t0).count();
-  stats.msRender = std::chrono::duration<double, std::milli>(tRendered - t0).count();
-  stats.msGather = std::chrono::duration<double, std::milli>(tEnd - tRendered).count();
-  status(R, 2, 1.f);
 }
 
 // samples: PathTraceIntegrator::requestSamples (pathtraceintegrator.cpp:35-47)
@@ -359,7 +371,7 @@ static FrameView frame_view(GpuCtx& g, const RendererObj& R, const FrameCache& f
 
 void Device::render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vector<CameraObj*>& C,
                           ToneMapperObj& T, int W, int H, int index, int count, int accumulate, bool reportProgress,
-                          float4* accu) {
+                          float4* accu, const AdaptivePass* pass) {
   const int nf = (int)C.size();
   HIP_CHECK(hipSetDevice(g.hipDevice));
   memset(&g.stats, 0, sizeof(g.stats));
@@ -398,7 +410,11 @@ void Device::render_shard(GpuCtx& g, GpuScene& G, RendererObj& R, const std::vec
 
   if (reportProgress) status(R, 1, 0.f);
   const int numTiles = rp.tilesPerFrame * nf;
-  s.shardTiles = shard_tiles(numTiles, index, count);
+  s.shardTiles = pass ? pass->count : shard_tiles(numTiles, index, count);
+  if (pass) {
+    s.tileList = pass->tileList;
+    s.half = pass->half;
+  }
 
   if (R.debug) {
     launch_debug_render(s.sv, s.fv, R.maxDepth, R.spp, numTiles, g.fbFloat(), g.fbRGB8(), (int)rgb8_row_stride(W),

@@ -107,6 +107,7 @@ PathBuffers ShardJob::lane_buffers(Lane& L) const {
   pb.shSegCap = pb.segCap * std::max(1, numDirect);
   // one light: shadow contributions are added by k_trace<true> itself (no resolve pass)
   pb.fuseShadow = numDirect == 1 && !s.sw.noShadowFuse;
+  pb.reserved = const_cast<int*>(s.tileList);  // list mode of batch_tile (kernels/yrt_camera.h)
   return pb;
 }
 
@@ -164,8 +165,9 @@ void ShardJob::start_batches() {
     const int64_t batchTiles = std::min<int64_t>(plan.tilesPerBatch, s.shardTiles - nextFirst);
     J.first = nextFirst;
     J.bi.firstTile = (int)nextFirst;
-    J.bi.tileStride = s.count;
-    J.bi.tileOffset = s.index;
+    // a listed batch names its tiles itself: the arithmetic members stay the identity
+    J.bi.tileStride = s.tileList ? 1 : s.count;
+    J.bi.tileOffset = s.tileList ? 0 : s.index;
     nextFirst += batchTiles;
     J.bi.numPixels = (int)(batchTiles * 256);
     J.bi.divPixels = fastdiv_make((uint32_t)J.bi.numPixels);
@@ -242,6 +244,8 @@ void ShardJob::enqueue_step(Lane& L, LaneJob& J) {
     L.pendCount += 1;
     launch_resolve_pixels(fv, pb, bi, g.fbFloat(), g.fbRGB8(), (int)rgb8_row_stride(s.rp.width),
                           g.accu, s.accumulate ? 1 : 0, st);
+    // an even iteration of an adaptive render: the same batch added into the half buffer, no display
+    if (s.half) launch_resolve_pixels(fv, pb, bi, nullptr, nullptr, 0, s.half, 1, st);
     J.active = false;
   }
   J.step += 1;
@@ -270,7 +274,7 @@ void ShardJob::run() {
   bool toeIn = false;
   for (const GpuCamera& c : g.hCams) toeIn |= c.type == CAM_STEREO && c.toeIn != 0;
   fusedPrimary = captureMax == 0 && !G.hasMotion && !s.fv.backplateTexels && s.sv.numEnvDir == 0 &&
-                 s.sw.primary != 0 && !toeIn;
+                 s.sw.primary != 0 && !toeIn && !s.tileList;  // PrimaryRays carries no tile list
   // A lane's batch is enqueued a step at a time — its prologue (counter clear, camera rays),
   // one depth (closest trace, shade, shadow trace), its epilogue (counter copy, pixel resolve)
   // — round-robin over the lanes that hold a batch, so every lane's first kernels are queued

@@ -34,6 +34,11 @@ struct ShardSetup {
   RenderSwitches sw;
   int index, count, shardTiles, accumulate;
   bool reportProgress;
+  // An adaptive render's iteration (adaptive.cpp): the shard is the shardTiles image tiles of
+  // tileList (a device array, ascending) instead of an arithmetic sequence, and every batch is
+  // also added into the half buffer when that is not null. null: a plain job.
+  const int* tileList = nullptr;
+  float4* half = nullptr;
 };
 
 class ShardJob {

@@ -314,6 +314,11 @@ void RtState::parseCommandLine(const std::vector<std::string>& tokens, const std
     } else if (tag == "-denoise") {
       denoise = cin.getInt();
       if (denoise < 0) throw std::runtime_error("-denoise: the iteration count must not be negative");
+    } else if (tag == "-adaptive") {
+      adaptiveThreshold = cin.getFloat();
+      adaptiveIterations = cin.getInt();
+      if (adaptiveIterations < 1) throw std::runtime_error("-adaptive: the iteration count must be at least 1");
+      adaptive = true;
     } else if (tag == "-denoise-albedo") {
       const int v = cin.getInt();
       if (v != 0 && v != 1) throw std::runtime_error("-denoise-albedo: 0 or 1 expected");
@@ -596,9 +601,22 @@ void RtState::renderFprFace(size_t i) {
     check(dev, yrtSetBool1(dev, cam, "toeIn", 1), "rtSetBool1");
     check(dev, yrtCommit(dev, cam), "rtCommit(camera)");
   }
-  check(dev, yrtRenderFrame(dev, renderer, cam, sc, tonemapper, frameBuffer, 0), "rtRenderFrame");
-  denoiseFrame(cam, sc, frameBuffer);
+  renderFrame(cam, sc);
   for (int j = 0; j < numBuffers; ++j) check(dev, yrtSwapBuffers(dev, frameBuffer), "rtSwapBuffers");
+}
+
+void RtState::renderFrame(YRTHandle cam, YRTHandle sc) {
+  if (adaptive) {
+    YRTAdaptiveParams p;
+    p.size = (uint32_t)sizeof(p);
+    if (yrtAdaptiveDefaults(&p) != 0) throw std::runtime_error("yrtAdaptiveDefaults failed");
+    p.threshold = adaptiveThreshold;
+    p.maxIterations = adaptiveIterations;
+    check(dev, yrtRenderAdaptive(dev, renderer, cam, sc, tonemapper, frameBuffer, &p, nullptr), "rtRenderAdaptive");
+  } else {
+    check(dev, yrtRenderFrame(dev, renderer, cam, sc, tonemapper, frameBuffer, 0), "rtRenderFrame");
+  }
+  denoiseFrame(cam, sc, frameBuffer);
 }
 
 YRTDenoiseParams RtState::denoiseParams() const {
@@ -694,7 +712,7 @@ void RtState::fprOutputMode() {
   std::vector<std::vector<uint8_t>> faces;
   // whole views as one job each (renderFprView) unless YRT_FACE_LOOP=1 asks for the
   // reference's face-by-face loop (same images)
-  const bool faceLoop = getenv("YRT_FACE_LOOP") != nullptr;
+  const bool faceLoop = getenv("YRT_FACE_LOOP") != nullptr || adaptive;  // -adaptive: a cube job keeps no accumulation
   bool viewDone = false;
   for (size_t i = 0; i < numViews && !(stopFlag && stopFlag->load()); ++i) {
     const size_t cubeFaceIndex = i % 12;
@@ -778,7 +796,8 @@ void RtState::outputMode(const std::string& fileName, std::vector<uint8_t>* outI
     const std::string base = fileName.empty() ? std::string() : fileName.substr(0, fileName.find_last_of('.'));
     // the 12 faces as one job (the scene does not change between them in this branch);
     // YRT_FACE_LOOP=1: the reference's face-by-face loop (same images)
-    const bool faceLoop = getenv("YRT_FACE_LOOP") != nullptr;
+    // -adaptive: face by face too (a multi-frame job keeps no accumulation to adapt by)
+    const bool faceLoop = getenv("YRT_FACE_LOOP") != nullptr || adaptive;
     if (!faceLoop) {
       std::vector<YRTHandle> cams;
       for (int i = 0; i < 12; ++i) cams.push_back(createCamera(i));
@@ -790,8 +809,7 @@ void RtState::outputMode(const std::string& fileName, std::vector<uint8_t>* outI
       if (faceLoop) {
         if (onStage) onStage(i, 12);
         YRTHandle cam = createCamera(i);
-        check(dev, yrtRenderFrame(dev, renderer, cam, sc, tonemapper, frameBuffer, 0), "rtRenderFrame");
-        denoiseFrame(cam, sc, frameBuffer);
+        renderFrame(cam, sc);
         for (int j = 0; j < numBuffers; ++j) check(dev, yrtSwapBuffers(dev, frameBuffer), "rtSwapBuffers");
         const uint8_t* p = (const uint8_t*)yrtMapFrameBuffer(dev, frameBuffer, -1);
         faces[i].assign(p, p + stride * height);
@@ -823,8 +841,7 @@ void RtState::outputMode(const std::string& fileName, std::vector<uint8_t>* outI
     check(dev, yrtSetInt1(dev, renderer, "showprogress", 1), "rtSetInt1");
     check(dev, yrtCommit(dev, renderer), "rtCommit(renderer)");
     for (int i = 0; i < numFrames; i++) {
-      check(dev, yrtRenderFrame(dev, renderer, cam, sc, tonemapper, frameBuffer, 0), "rtRenderFrame");
-      denoiseFrame(cam, sc, frameBuffer);
+      renderFrame(cam, sc);
     }
     for (int i = 0; i < numBuffers; i++) check(dev, yrtSwapBuffers(dev, frameBuffer), "rtSwapBuffers");
     const uint8_t* p = (const uint8_t*)yrtMapFrameBuffer(dev, frameBuffer, -1);

@@ -107,6 +107,11 @@ struct RtState {
   int denoise = 0;  // -denoise <iterations>: a-trous passes over every rendered frame (0: off)
   bool denoiseAlbedo = false;  // -denoise-albedo <0|1>: demodulate by the first-hit albedo (with -denoise)
   bool denoiseCube = false;  // -denoise-cube <0|1>: renderCube filters its faces as one surface (with -denoise)
+  // -adaptive <threshold> <maxIterations>: every frame rendered into frameBuffer is an adaptive
+  // render (yrtRenderAdaptive) of -spp samples per iteration; the stereo branch then renders face by face
+  bool adaptive = false;
+  float adaptiveThreshold = 0.f;
+  int adaptiveIterations = 1;
   int width = 512, height = 512;
   std::string format = "RGB8";
   std::string outFileName;
@@ -128,6 +133,9 @@ struct RtState {
   void parseCommandLine(const std::vector<std::string>& tokens, const std::string& path);
   YRTHandle createCamera(int face);
   YRTHandle createScene();
+  // one frame through cam into frameBuffer: yrtRenderFrame(..., 0), or with -adaptive
+  // yrtRenderAdaptive; then -denoise
+  void renderFrame(YRTHandle cam, YRTHandle sc);
   // -denoise: filters the frame just rendered into fb through cam (yrtDenoiseFrameBuffer with the
   // library's default weights; -denoise-albedo 1: demodulated, albedoPower = 1 / gamma), before it
   // is read, watermarked or assembled into a strip

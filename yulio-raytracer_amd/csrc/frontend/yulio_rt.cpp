@@ -157,8 +157,7 @@ void* yrtSessionRender(YRTSession s, int face) {
     RtState& st = s->st;
     YRTHandle sc = st.createScene();
     YRTHandle cam = st.createCamera(face);
-    check(st.dev, yrtRenderFrame(st.dev, st.renderer, cam, sc, st.tonemapper, st.frameBuffer, 0), "rtRenderFrame");
-    st.denoiseFrame(cam, sc, st.frameBuffer);
+    st.renderFrame(cam, sc);
     return yrtMapFrameBuffer(st.dev, st.frameBuffer, -1);
   } catch (const std::exception& e) {
     g_feError = e.what();

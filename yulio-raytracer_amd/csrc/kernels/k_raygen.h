@@ -36,7 +36,7 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_raygen(FrameView fv, PathBuffers 
     // multiple of 256): computed once from the block base, on the scalar unit
     const int s = fastdiv(base, bi.divPixels);
     int x0 = 0, y0 = 0, f = 0;
-    const bool tileOk = batch_tile(rp, bi, (base - s * bi.numPixels) >> 8, x0, y0, f);
+    const bool tileOk = batch_tile(rp, bi, (base - s * bi.numPixels) >> 8, x0, y0, f, (const int*)pb.reserved);
     const int x = x0 + (p & 15), y = y0 + ((p >> 4) & 15);
     // a pixel of the image, and the loop head of Li: depth < maxDepth and
     // max(throughput) = 1 >= minContribution

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(YRT_BLOCK) __attribute__((amdgpu_waves_per_eu(
       medium = (meta >> 10) & 0xFFFF;  // LightPath::lastMedium as a medium-table index
       s = fastdiv(path, bi.divPixels);
       const int i = path - s * bi.numPixels;
-      batch_pixel(rp, bi, i, px, py);
+      batch_pixel(rp, bi, i, px, py, (const int*)pb.reserved);
       pixelId = py * rp.width + px;
       isHit = __float_as_int(h.w) >= 0;
     }
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(YRT_BLOCK) void k_resolve_pixels(FrameView fv, Path
   const size_t frameStride = (size_t)rp.width * rp.height;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < bi.numPixels; i += gridDim.x * blockDim.x) {
     int x, y, f;
-    if (!batch_pixel(rp, bi, i, x, y, f)) continue;
+    if (!batch_pixel(rp, bi, i, x, y, f, (const int*)pb.reserved)) continue;
     V3 L = v3s(0.f);
     for (int s = 0; s < rp.spp; ++s) {
       const float4 l4 = pb.pathL[(size_t)s * bi.numPixels + i];

@@ -34,6 +34,7 @@
 #include "k_checks.h"
 #include "k_sample_dirs.h"
 #include "k_refit.h"
+#include "k_adaptive.h"
 
 namespace yrt {
 
@@ -168,6 +169,20 @@ void launch_resolve_pixels(const FrameView& fv, const PathBuffers& pb, const Bat
                            uint8_t* fbRGB8, int rgb8Stride, float4* accu, int accumulate, hipStream_t s) {
   hipLaunchKernelGGL(k_resolve_pixels, dim3(grid_for(bi.numPixels, YRT_BLOCK, 8192)), dim3(YRT_BLOCK), 0, s, fv, pb, bi,
                      fbFloat, fbRGB8, rgb8Stride, accu, accumulate);
+}
+
+void launch_tile_error(const float4* accu, const float4* half, int width, int height, int numTilesX, const int* list,
+                       int count, float threshold, int iterations, float* tileError, int* tileIterations, int* stopped,
+                       hipStream_t s) {
+  if (count <= 0) return;
+  hipLaunchKernelGGL(k_tile_error, dim3(count), dim3(YRT_ADAPTIVE_BLOCK), 0, s, accu, half, width, height, numTilesX,
+                     list, count, threshold, iterations, tileError, tileIterations, stopped);
+}
+
+void launch_tile_compact(const int* listIn, const int* stopped, int count, int* listOut, int* countOut, hipStream_t s) {
+  if (count <= 0) return;
+  hipLaunchKernelGGL(k_tile_compact, dim3((count + YRT_ADAPTIVE_BLOCK - 1) / YRT_ADAPTIVE_BLOCK),
+                     dim3(YRT_ADAPTIVE_BLOCK), 0, s, listIn, stopped, count, listOut, countOut);
 }
 
 void launch_pack_tiles(const float* fbFloat, const uint8_t* fbRGB8, const SlabLayout& L, int numTiles, void* slab,

@@ -107,12 +107,22 @@ template <class D>  // FastDiv, or a YRT_CONST one
 __device__ __forceinline__ int fastdiv(int n, const D& d) {  // n in [0, 2^31)
   return (int)((__umulhi((unsigned)n, d.mul) + (unsigned)n) >> d.shift);
 }
-// the tile of batch-pixel block ib = i >> 8: its frame and first pixel (false past the job)
+// the tile of batch-pixel block ib = i >> 8: its frame and first pixel (false past the job).
+// tileList (PathBuffers::reserved) != null: a batch of an adaptive render (device/adaptive.cpp),
+// whose tiles are the image tiles tileList[firstTile + ib] of one unsharded frame (ib below the
+// batch's tiles: the list ends with the last batch).
 template <class RP>
 __device__ __forceinline__ bool batch_tile(const RP& rp, const BatchInfo& bi, int ib, int& x0, int& y0,
-                                           int& f) {
-  int tile = bi.tileOffset + (bi.firstTile + ib) * bi.tileStride;
+                                           int& f, const int* tileList = nullptr) {
   f = 0;
+  if (tileList) {
+    const int t = tileList[bi.firstTile + ib];
+    const int ty = fastdiv(t, rp.divTilesX);
+    x0 = (t - ty * rp.numTilesX) * 16;
+    y0 = ty * 16;
+    return true;
+  }
+  int tile = bi.tileOffset + (bi.firstTile + ib) * bi.tileStride;
   if (tile >= rp.tilesPerFrame * rp.numFrames) return false;
   if (rp.numFrames > 1) {
     f = fastdiv(tile, rp.divTilesPerFrame);
@@ -127,17 +137,18 @@ __device__ __forceinline__ bool batch_tile(const RP& rp, const BatchInfo& bi, in
 }
 template <class RP>
 __device__ __forceinline__ bool batch_pixel(const RP& rp, const BatchInfo& bi, int i, int& x, int& y,
-                                            int& f) {
+                                            int& f, const int* tileList = nullptr) {
   int x0 = 0, y0 = 0;
-  if (!batch_tile(rp, bi, i >> 8, x0, y0, f)) return false;
+  if (!batch_tile(rp, bi, i >> 8, x0, y0, f, tileList)) return false;
   x = x0 + (i & 15);
   y = y0 + ((i >> 4) & 15);
   return x < rp.width && y < rp.height;
 }
 template <class RP>
-__device__ __forceinline__ bool batch_pixel(const RP& rp, const BatchInfo& bi, int i, int& x, int& y) {
+__device__ __forceinline__ bool batch_pixel(const RP& rp, const BatchInfo& bi, int i, int& x, int& y,
+                                            const int* tileList = nullptr) {
   int f;
-  return batch_pixel(rp, bi, i, x, y, f);
+  return batch_pixel(rp, bi, i, x, y, f, tileList);
 }
 
 __device__ __forceinline__ float samp(const FrameView& fv, int dim, int rec) {

@@ -104,8 +104,9 @@ struct PathBuffers {
   float4* qDir[2];   // xyz, tfar
   float4* qThr[2];   // throughput xyz, w = meta bits: depth | ignoreVL<<8 | unbent<<9
   float4* hit;       // t, u, v, tri (bits), per closest-queue slot
-  void* reserved = nullptr;  // unused: keeps the kernel-argument offsets of everything below, which
-                             // k_shade's scalar-load grouping and SGPR spills depend on
+  void* reserved = nullptr;  // null, or the tile list of an adaptive render's batch (const int*, batch_tile in
+                             // yrt_camera.h). The member keeps the kernel-argument offsets of everything below,
+                             // which k_shade's scalar-load grouping and SGPR spills depend on
   float4* pathL;     // per path id: radiance so far (emission and unoccluded direct light are
                      // read-modify-written in the reference's order; one writer per path at a time)
   int* shFirst;      // per (queue slot, light): shadow-ray slot or -1
@@ -186,6 +187,15 @@ void launch_shade(const SceneView& sv, const FrameView& fv, const PathBuffers& p
 void launch_shadow_resolve(const PathBuffers& pb, int depth, int numLights, hipStream_t s);
 void launch_resolve_pixels(const FrameView& fv, const PathBuffers& pb, const BatchInfo& bi, float* fbFloat,
                            uint8_t* fbRGB8, int rgb8Stride, float4* accu, int accumulate, hipStream_t s);
+// The check of an adaptive render (k_adaptive.h), on one W x H frame of numTilesX tile columns.
+// launch_tile_error: E_T (common/yrt_tile_error.h) of the `count` image tiles list[j] from the sums
+// accu and the half sums `half`; stores tileError[tile], tileIterations[tile] = iterations and
+// stopped[j] = E_T < threshold. launch_tile_compact: listOut = the entries of listIn whose flag is
+// 0, in listIn's order, and *countOut = their number (device pointers; listOut is not listIn).
+void launch_tile_error(const float4* accu, const float4* half, int width, int height, int numTilesX, const int* list,
+                       int count, float threshold, int iterations, float* tileError, int* tileIterations, int* stopped,
+                       hipStream_t s);
+void launch_tile_compact(const int* listIn, const int* stopped, int count, int* listOut, int* countOut, hipStream_t s);
 // YRT_PROFILE builds only: SIMD-utilization counters of k_trace (see yrt_wave.h); -1 otherwise
 int trace_profile(unsigned long long* out8, int reset);
 // Debug capture: per-sample radiance of pixel id (y * width + x) of frame `frame` written to

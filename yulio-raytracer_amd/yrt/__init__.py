@@ -352,6 +352,46 @@ class Device:
     def rtSwapBuffers(self, frameBuffer):
         self._rc(N.dev.yrtSwapBuffers(self.h, frameBuffer), "rtSwapBuffers")
 
+    # -- adaptive sampling (yrt_device.h: converged tiles stop, only the active ones render)
+    @staticmethod
+    def adaptive_defaults() -> dict:
+        """The library's default YRTAdaptiveParams."""
+        p = N.AdaptiveParams(size=C.sizeof(N.AdaptiveParams))
+        if N.dev.yrtAdaptiveDefaults(C.byref(p)) != 0:
+            raise RuntimeError("yrtAdaptiveDefaults failed")
+        return {"threshold": p.threshold, "min_iterations": p.minIterations, "max_iterations": p.maxIterations}
+
+    def rtRenderAdaptive(self, renderer, camera, scene, toneMapper, frameBuffer, threshold=None, max_iterations=None,
+                         min_iterations=None) -> dict:
+        """yrtRenderAdaptive: one frame in progressive iterations of the renderer's spp; a 16x16
+        tile stops once its error estimate (tile_error) is below `threshold`. None: the library's
+        default. Returns the call's YRTAdaptiveStats (iterations, tiles, tilesStopped, samples,
+        msTotal, msError)."""
+        p = N.AdaptiveParams(size=C.sizeof(N.AdaptiveParams))
+        if N.dev.yrtAdaptiveDefaults(C.byref(p)) != 0:
+            raise RuntimeError("yrtAdaptiveDefaults failed")
+        if threshold is not None:
+            p.threshold = float(threshold)
+        if min_iterations is not None:
+            p.minIterations = int(min_iterations)
+        if max_iterations is not None:
+            p.maxIterations = int(max_iterations)
+        st = N.AdaptiveStats(size=C.sizeof(N.AdaptiveStats))
+        self._rc(N.dev.yrtRenderAdaptive(self.h, renderer, camera, scene, toneMapper, frameBuffer, C.byref(p),
+                                         C.byref(st)), "rtRenderAdaptive")
+        return {n: getattr(st, n) for n, _ in st._fields_ if n != "size"}
+
+    def adaptive_tiles(self, frameBuffer):
+        """(iterations int32, error float32) per tile of frameBuffer's last adaptive render, image
+        tile order, row-major; error is +inf for a tile no check looked at (yrtGetAdaptiveTiles)."""
+        n = N.dev.yrtGetAdaptiveTiles(self.h, frameBuffer, None, None, 0)
+        self._rc(min(n, 0), "adaptive_tiles")
+        it, err = np.zeros(n, np.int32), np.zeros(n, np.float32)
+        if n:
+            self._rc(min(N.dev.yrtGetAdaptiveTiles(self.h, frameBuffer, it.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   err.ctypes.data_as(N.PF), n), 0), "adaptive_tiles")
+        return it, err
+
     # -- denoise (yrt_device.h: first-hit guide buffers + edge-avoiding a-trous filter)
     def render_guides(self, camera, scene, width, height):
         """(pos4, nrm4), float32 (height, width, 4) each: the first hit of the camera ray through
@@ -659,6 +699,22 @@ class ShardHub:
         if r < 0:
             raise RuntimeError(N.dev.yrtShardHubLastError().decode())
         return out[:(self.world - 1) * recv_bytes_per_rank] if out is not None else None
+
+
+def tile_error(accu, half):
+    """E_T of every 16x16 tile of a frame from its sums `accu` and half sums `half`, float32
+    (height, width, 4) arrays of (r, g, b, weight): the estimate adaptive renders stop tiles by
+    (csrc/common/yrt_tile_error.h, on the host), float32 (tiles_y, tiles_x)."""
+    accu = np.ascontiguousarray(accu, np.float32)
+    half = np.ascontiguousarray(half, np.float32)
+    if accu.ndim != 3 or accu.shape[2] != 4 or half.shape != accu.shape:
+        raise ValueError("accu and half: float32 arrays of one shape (height, width, 4)")
+    h, w = accu.shape[:2]
+    out = np.zeros(((h + 15) // 16, (w + 15) // 16), np.float32)
+    if N.dev.yrtDebugTileError(accu.ctypes.data_as(N.PF), half.ctypes.data_as(N.PF), w, h,
+                               out.ctypes.data_as(N.PF)) != 0:
+        raise ValueError("tile_error: empty frame")
+    return out
 
 
 def cube_tap(W, face, qx, qy):

@@ -87,6 +87,17 @@ class DenoiseParams(C.Structure):
                 ("sigmaPosition", f32), ("demodulate", i32), ("albedoPower", f32), ("albedoFloor", f32)]
 
 
+class AdaptiveParams(C.Structure):
+    """include/yrt_device.h YRTAdaptiveParams; size = the bytes the caller's struct holds."""
+    _fields_ = [("size", C.c_uint32), ("threshold", f32), ("minIterations", i32), ("maxIterations", i32)]
+
+
+class AdaptiveStats(C.Structure):
+    """include/yrt_device.h YRTAdaptiveStats; size = the bytes the caller's struct holds."""
+    _fields_ = [("size", C.c_uint32), ("iterations", C.c_int32), ("tiles", C.c_int64), ("tilesStopped", C.c_int64),
+                ("samples", C.c_double), ("msTotal", C.c_double), ("msError", C.c_double)]
+
+
 def _sig(lib, name, res, *args):
     fn = getattr(lib, name)
     fn.restype = res
@@ -230,6 +241,13 @@ except AttributeError:
 try:  # the cube denoise; absent from older builds selected with YRT_LIB_DIR
     _sig(dev, "yrtDenoiseCube", i32, vp, C.POINTER(vp), i32, vp, C.POINTER(vp), C.POINTER(DenoiseParams))
     _sig(dev, "yrtDebugCubeTap", i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32))
+except AttributeError:
+    pass
+try:  # adaptive sampling; absent from older builds selected with YRT_LIB_DIR
+    _sig(dev, "yrtAdaptiveDefaults", i32, C.POINTER(AdaptiveParams))
+    _sig(dev, "yrtRenderAdaptive", i32, vp, vp, vp, vp, vp, vp, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats))
+    _sig(dev, "yrtGetAdaptiveTiles", i32, vp, vp, C.POINTER(C.c_int32), PF, sz)
+    _sig(dev, "yrtDebugTileError", i32, PF, PF, i32, i32, PF)
 except AttributeError:
     pass
 _sig(dev, "yrtDebugDecodeImage", i32, cstr, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, sz)
