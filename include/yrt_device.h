@@ -213,13 +213,29 @@ YRT_API int yrtRenderAlbedo(YRTDevice dev, YRTHandle camera, YRTHandle scene, in
  * (a L)^(1/gamma) = a^(1/gamma) L^(1/gamma); the vignette is a per-pixel factor and cancels.
  * albedoFloor keeps the division away from 0. Both must be finite and > 0 and are checked only when
  * demodulate is set; demodulate = 0 (the default, and a struct that ends before it) is the plain
- * filter, bit for bit. Defaults: 0, 1, 1/255. */
+ * filter, bit for bit. Defaults: 0, 1, 1/255.
+ * varianceGuided != 0: the variance-guided filter (after SVGF, Schied et al. 2017) for a frame whose
+ * framebuffer holds an adaptive render (yrtRenderAdaptive; threshold 0 and maxIterations K are K
+ * plain progressive frames). The per-pixel variance of the displayed frame (yrtFrameVariance) is
+ * summed over the channels (divided by m^2 per channel when demodulate is set) and filtered along
+ * with the colour, v' = sum w^2 v / (sum w)^2, and the colour weight becomes
+ * exp(-|dc|^2 / (sigmaVariance^2 vbar + varianceFloor)), vbar the 3x3 Gaussian mean of the
+ * variance around the pixel; sigmaColor is not read and nothing tightens with the step.
+ * varianceFloor keeps flat regions filtering: (1/255)^2, the square of an 8-bit step. Both must be
+ * finite and > 0 and are checked only when varianceGuided is set. The call is refused, and writes
+ * nothing, unless every framebuffer's last frame is an adaptive render on this device in which
+ * every tile ran at least 2 iterations. varianceGuided = 0 (the default, and a struct that ends
+ * before it) is the filter above, bit for bit. Defaults: 0, 3, (1/255)^2. Known limit: on an
+ * emitter's edge the honest variance is large and the light bleeds onto coplanar surfaces around it
+ * (DESIGN.md §9). */
 typedef struct YRTDenoiseParams {
   uint32_t size;
   int iterations;
   float sigmaColor, sigmaNormal, sigmaPosition;
   int demodulate;
   float albedoPower, albedoFloor;
+  int varianceGuided;
+  float sigmaVariance, varianceFloor;
 } YRTDenoiseParams;
 /* Fills the fields that fit into p->size (set by the caller) with the library's defaults. */
 YRT_API int yrtDenoiseDefaults(YRTDenoiseParams* p);
@@ -251,10 +267,27 @@ YRT_API int yrtDenoiseCube(YRTDevice dev, const YRTHandle* cameras, int numFrame
  * a tap that lands on a face, 0 for a skipped corner tap, -1 for arguments out of range (W outside
  * 1..16384, a tap farther than 2^17 pixels from the face, a null pointer). */
 YRT_API int yrtDebugCubeTap(int W, int face, int qx, int qy, int* g, int* x, int* y);
+/* The variance frame of the framebuffer's last adaptive render, the counterpart of yrtRenderGuides
+ * for the variance-guided filter: var4Host[4 i] = (v_r, v_g, v_b, 1), i = y * width + x,
+ * width * height * 4 floats. With the sums S (weight w) and the half sums H (weight h, the even
+ * iterations) of the render and r = w - h: A = H rcp(h), B = max(S - H, 0) rcp(r), both mapped as
+ * the render's tone mapper displays them (pow 1 / gamma iff gamma != 1, then the vignette iff set),
+ * v_c = (dA_c - dB_c)^2 (h r) rcp(w)^2, the variance of the displayed mean of the two halves; a v_c
+ * that is not finite is 0. Refused as the variance-guided filter is: after any other render into
+ * the framebuffer, on another device, or when a tile ran fewer than 2 iterations. */
+YRT_API int yrtFrameVariance(YRTDevice dev, YRTHandle framebuffer, float* var4Host);
+/* The framebuffer's size in pixels (what sizes var4Host); either pointer may be NULL. */
+YRT_API int yrtGetFrameBufferSize(YRTDevice dev, YRTHandle framebuffer, int* width, int* height);
+/* Host-side: the same estimate by the header the kernel compiles (csrc/common/yrt_pixel_variance.h)
+ * from sums accu4 and half sums half4 ([height][width][4] floats: r, g, b, weight) into var4 (the
+ * same shape). With gamma 1 and vignetting 0 it equals the device's bit for bit. -1 on a null
+ * pointer or an empty frame. */
+YRT_API int yrtDebugFrameVariance(const float* accu4, const float* half4, int width, int height, float gamma,
+                                  int vignetting, float* var4);
 /* With yrtSetKernelTiming on: HIP-event times, in ms, of the kernels of the last guide pass
  * (yrtRenderGuides, yrtRenderAlbedo, or the one inside yrtDenoiseFrameBuffer / yrtDenoiseCube, which renders the
  * albedo in the same kernel when demodulate is set) and of the last filter (its load and
- * iterations, without the guide pass and any host copy). Either pointer may be NULL. */
+ * iterations and, variance-guided, its variance pass; without the guide pass and any host copy). Either pointer may be NULL. */
 YRT_API int yrtGetDenoiseTimes(YRTDevice dev, float* msGuides, float* msFilter);
 /* Renderer status callback (device.h:335-347): state 0 Inactive, 1 Rendering, 2 Done. */
 typedef void (*YRTStatusCallback)(int state, float progress, void* user);

@@ -34,6 +34,10 @@ typedef struct YRTSessionInfo {
 } YRTSessionInfo;
 /* Commits the scene (createScene) on first call and returns the session's handles. */
 YRT_API int yrtSessionInfo(YRTSession s, YRTSessionInfo* out);
+/* What the session's -denoise / -denoise-albedo / -denoise-variance tags pass to the denoise calls:
+ * the fields the session sets, up to out->size (set by the caller); out->size returns the bytes
+ * that hold them, the fields beyond being left to the library's defaults. */
+YRT_API int yrtSessionDenoiseParams(YRTSession s, YRTDenoiseParams* out);
 /* Camera of the session: face -1 = mono pinhole (createCamera), 0..11 = stereo cube faces
  * (renderer.cpp:747-757). The handle is owned by the session. */
 YRT_API YRTHandle yrtSessionCamera(YRTSession s, int face);

@@ -54,6 +54,12 @@ void Device::render_adaptive(RendererObj& R, CameraObj& C, SceneObj& S, ToneMapp
   GpuScene& G = scene_on(S, g.hipDevice, true);
   float4* const accu = frame_accu(F, g);
   float4* const half = frame_half(F, g);
+  for (const auto& a : F.adaptive)
+    if (a->ctxSerial == g.serial) {  // the display mapping of this render's resolves (render.cpp)
+      a->gamma = T.gamma;
+      a->rcpGamma = rcpf_(T.gamma);
+      a->vignetting = T.vignetting;
+    }
   HIP_CHECK(hipMemsetAsync(half, 0, (size_t)W * H * sizeof(float4), g.stream));
 
   // every tile active, in image order; no tile checked yet

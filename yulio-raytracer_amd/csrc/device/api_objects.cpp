@@ -5,6 +5,7 @@
 #include <strings.h>
 
 #include "../common/yrt_cube_tap.h"
+#include "../common/yrt_pixel_variance.h"
 #include "device.h"
 #include "image_io.h"
 
@@ -691,6 +692,13 @@ static YRTDenoiseParams denoise_params(const YRTDenoiseParams* p) {
   d.demodulate = 0;
   d.albedoPower = 1.0f;
   d.albedoFloor = 1.0f / 255.0f;
+  // sigmaVariance 3: the lowest sum of the four below-1 error ratios (C1 and C2 after 2 and 8
+  // iterations) among 1, 2, 3, 4 in the CPU rehearsal (tools/denoise_variance_rehearsal.py, §9).
+  // varianceFloor (1/255)^2: the square of an 8-bit step, so a byte frame's quantisation never
+  // reads as signal.
+  d.varianceGuided = 0;
+  d.sigmaVariance = 3.0f;
+  d.varianceFloor = (1.0f / 255.0f) * (1.0f / 255.0f);
   if (!p) return d;
   if (p->size < sizeof(uint32_t)) throw std::runtime_error("YRTDenoiseParams: size is smaller than the size field");
   const size_t n = p->size;
@@ -703,6 +711,9 @@ static YRTDenoiseParams denoise_params(const YRTDenoiseParams* p) {
   YRT_DN_FIELD(demodulate);
   YRT_DN_FIELD(albedoPower);
   YRT_DN_FIELD(albedoFloor);
+  YRT_DN_FIELD(varianceGuided);
+  YRT_DN_FIELD(sigmaVariance);
+  YRT_DN_FIELD(varianceFloor);
 #undef YRT_DN_FIELD
   if (d.iterations < 0 || d.iterations > 16) throw std::runtime_error("YRTDenoiseParams: iterations outside 0..16");
   if (!(d.sigmaNormal >= 0.f) || !(d.sigmaPosition > 0.f) || d.sigmaColor != d.sigmaColor)
@@ -712,6 +723,10 @@ static YRTDenoiseParams denoise_params(const YRTDenoiseParams* p) {
     throw std::runtime_error("YRTDenoiseParams: demodulate needs a finite albedoPower > 0");
   if (d.demodulate != 0 && !positive(d.albedoFloor))
     throw std::runtime_error("YRTDenoiseParams: demodulate needs a finite albedoFloor > 0");
+  if (d.varianceGuided != 0 && !positive(d.sigmaVariance))
+    throw std::runtime_error("YRTDenoiseParams: varianceGuided needs a finite sigmaVariance > 0");
+  if (d.varianceGuided != 0 && !positive(d.varianceFloor))
+    throw std::runtime_error("YRTDenoiseParams: varianceGuided needs a finite varianceFloor > 0");
   return d;
 }
 
@@ -838,6 +853,39 @@ int yrtDenoiseCube(YRTDevice dev, const YRTHandle* cameras, int numFrames, YRTHa
   D.denoise(C, *S, F, dp, true, "yrtDenoiseCube");
   return 0;
   DEV_END(-1)
+}
+
+int yrtFrameVariance(YRTDevice dev, YRTHandle framebuffer, float* var4Host) {
+  DEV_GUARD(dev, -1)
+  Device& D = *dev->d;
+  if (!D.gpu) throw std::runtime_error("yrtFrameVariance: host-only device (created with parms \"host\")");
+  auto F = D.get<FrameBufferObj>(framebuffer, "framebuffer");
+  if (!F || !var4Host) throw std::runtime_error("yrtFrameVariance: null handle or pointer");
+  D.frame_variance(*F, var4Host);
+  return 0;
+  DEV_END(-1)
+}
+
+int yrtGetFrameBufferSize(YRTDevice dev, YRTHandle framebuffer, int* width, int* height) {
+  DEV_GUARD(dev, -1)
+  auto F = dev->d->get<FrameBufferObj>(framebuffer, "framebuffer");
+  if (!F) throw std::runtime_error("yrtGetFrameBufferSize: null handle");
+  if (width) *width = F->width;
+  if (height) *height = F->height;
+  return 0;
+  DEV_END(-1)
+}
+
+int yrtDebugFrameVariance(const float* accu4, const float* half4, int width, int height, float gamma, int vignetting,
+                          float* var4) {
+  if (!accu4 || !half4 || !var4 || width < 1 || height < 1) return -1;
+  const float rcpGamma = rcpf_(gamma);  // as the render's resolve has it
+  for (int y = 0; y < height; ++y)
+    for (int x = 0; x < width; ++x) {
+      const size_t o = ((size_t)y * width + x) * 4;
+      yrt_pixel_variance(accu4 + o, half4 + o, x, y, width, height, gamma, rcpGamma, vignetting ? 1 : 0, var4 + o);
+    }
+  return 0;
 }
 
 int yrtGetDenoiseTimes(YRTDevice dev, float* msGuides, float* msFilter) {

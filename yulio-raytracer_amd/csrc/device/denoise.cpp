@@ -50,6 +50,50 @@ Device::FilterFrame Device::filter_frame(FrameBufferObj& F, int id) {
   return ff;
 }
 
+// The sums and half sums the variance of F's displayed frame is estimated from
+// (common/yrt_pixel_variance.h): those of F's last render, which must have been an adaptive render
+// on ctx[0] in which every tile ran at least two iterations, so that both halves hold samples.
+// Judged from host records alone: a refusal launches and writes nothing.
+Device::VarianceSource Device::variance_source(FrameBufferObj& F, const char* what) {
+  const std::string w(what);
+  if (!F.accuFromAdaptive)
+    throw std::runtime_error(w + ": the framebuffer's last frame is not an adaptive render (rtRenderAdaptive keeps the "
+                                 "half buffer the variance is estimated from)");
+  VarianceSource v;
+  for (const auto& a : F.accu)
+    if (a->ctxSerial == ctx[0]->serial) v.accu = a->sums.as<float4>();
+  for (const auto& a : F.adaptive)
+    if (a->ctxSerial == ctx[0]->serial) {
+      v.half = a->half.as<float4>();
+      v.gamma = a->gamma;
+      v.rcpGamma = a->rcpGamma;
+      v.vignetting = a->vignetting ? 1 : 0;
+    }
+  if (!v.accu || !v.half)
+    throw std::runtime_error(w + ": the framebuffer's adaptive render ran on another device (its sums are not on this one)");
+  if (F.tileIterations.empty()) throw std::runtime_error(w + ": the framebuffer has no tile records of an adaptive render");
+  for (int32_t n : F.tileIterations)
+    if (n < 2)
+      throw std::runtime_error(w + ": a tile of the adaptive render ran fewer than 2 iterations (maxIterations 1 or a "
+                                   "stop after the first): one half has no samples");
+  return v;
+}
+
+// yrtFrameVariance: var4 of F's last adaptive render, [H][W][4] floats, to the host
+void Device::frame_variance(FrameBufferObj& F, float* var4Host) {
+  const VarianceSource v = variance_source(F, "yrtFrameVariance");
+  const int W = F.width, H = F.height;
+  if (W < 1 || H < 1) return;
+  HIP_CHECK(hipSetDevice(hipDevice));
+  GpuCtx& g = *ctx[0];
+  const size_t bytes = (size_t)W * H * sizeof(float4);
+  g.dFilterVar.alloc(bytes);
+  launch_frame_variance(v.accu, v.half, W, H, v.gamma, v.rcpGamma, v.vignetting, g.dFilterVar.as<float4>(), stream);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(var4Host, g.dFilterVar.p, bytes, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+}
+
 // yrtDenoiseFrameBuffer / yrtDenoiseCube: the filter over a surface of C.size() frames of one size
 // and format, F[k] seen through C[k]: one frame whose taps stop at its border, or (wrap) the 6 or
 // 12 square faces of a stereo cube in slot order k = eye * 6 + cubeFaceIndex % 6, which the caller
@@ -65,10 +109,17 @@ Device::FilterFrame Device::filter_frame(FrameBufferObj& F, int id) {
 // demodulate: the guide pass also renders the first-hit albedo, the load divides the frames by the
 // modulation max(albedo, albedoFloor) ^ albedoPower and the last iteration multiplies it back
 // (k_atrous<true>); clear, the kernels are the <false> instantiations: no albedo.
+// varianceGuided: every frame must hold an adaptive render (variance_source, judged before anything
+// is launched); k_frame_variance fills a [face][H][W] variance array from each face's own sums and
+// half sums, inside the timed filter, and the _var kernels run in place of the plain ones.
 void Device::denoise(const std::vector<CameraObj*>& C, SceneObj& S, const std::vector<FrameBufferObj*>& F,
                      const YRTDenoiseParams& p, bool wrap, const char* what) {
   // also of a call that filters nothing (below), which never reaches the guide pass
   if (!S.gpu) throw std::runtime_error(std::string(what) + ": scene not committed");
+  const bool variance = p.varianceGuided != 0;
+  std::vector<VarianceSource> vs;
+  if (variance)
+    for (FrameBufferObj* f : F) vs.push_back(variance_source(*f, what));
   if (p.iterations == 0) return;
   const int faces = (int)C.size(), W = F[0]->width, H = F[0]->height;
   if (W < 1 || H < 1) return;
@@ -114,8 +165,17 @@ void Device::denoise(const std::vector<CameraObj*>& C, SceneObj& S, const std::v
     dm.albedoFloor = p.albedoFloor;
     dm.albedoPower = p.albedoPower;
   }
+  if (variance) g.dFilterVar.alloc(frameBytes);
   evFilter.time(kernelTiming, stream, [&] {
-    launch_atrous_load(g.dFaceIo.as<FrameIO>(), faces, W, H, g.dFilter[0].as<float4>(), dm, stream);
+    if (variance) {
+      for (int k = 0; k < faces; ++k)
+        launch_frame_variance(vs[k].accu, vs[k].half, W, H, vs[k].gamma, vs[k].rcpGamma, vs[k].vignetting,
+                              g.dFilterVar.as<float4>() + (size_t)k * W * H, stream);
+      launch_atrous_load_var(g.dFaceIo.as<FrameIO>(), faces, W, H, g.dFilter[0].as<float4>(), dm,
+                             g.dFilterVar.as<float4>(), g.dGuidePos.as<float4>(), stream);
+    } else {
+      launch_atrous_load(g.dFaceIo.as<FrameIO>(), faces, W, H, g.dFilter[0].as<float4>(), dm, stream);
+    }
     AtrousParams ap;
     memset(&ap, 0, sizeof(ap));
     ap.width = W;
@@ -128,9 +188,15 @@ void Device::denoise(const std::vector<CameraObj*>& C, SceneObj& S, const std::v
       // sigmaColor_i = sigmaColor 2^-i (Dammertz et al.): the colour weight tightens as the taps spread
       const float sc = p.sigmaColor > 0.f ? p.sigmaColor / (float)(1 << i) : 0.f;
       ap.rcpSigmaColor2 = sc > 0.f ? 1.0f / (sc * sc) : 0.f;
-      launch_atrous(ap, faces, wrap, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(), g.dFilter[i & 1].as<float4>(),
-                    last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(), last ? g.dFaceIo.as<FrameIO>() : nullptr,
-                    dm.mod4, stream);
+      if (variance)  // no 2^-i tightening: the filtered variance itself shrinks
+        launch_atrous_var(ap, faces, wrap, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(),
+                          g.dFilter[i & 1].as<float4>(), last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(),
+                          last ? g.dFaceIo.as<FrameIO>() : nullptr, dm.mod4, p.sigmaVariance * p.sigmaVariance,
+                          p.varianceFloor, stream);
+      else
+        launch_atrous(ap, faces, wrap, g.dGuidePos.as<float4>(), g.dGuideNrm.as<float4>(),
+                      g.dFilter[i & 1].as<float4>(), last ? nullptr : g.dFilter[(i + 1) & 1].as<float4>(),
+                      last ? g.dFaceIo.as<FrameIO>() : nullptr, dm.mod4, stream);
     }
   });
   HIP_CHECK(hipGetLastError());

@@ -107,6 +107,8 @@ struct GpuCtx {
   // the guide frames, the filter's two ping-pong float4 frames, the modulation, the uploads of the
   // frames that live in host pixels and the FrameIO records; the cameras go to dCam
   DevBuf dGuidePos, dGuideNrm, dGuideAlbedo, dFilter[2], dFilterMod, dFilterFb, dFaceIo;
+  // the variance frames (var4) of the variance-guided filter and of yrtFrameVariance
+  DevBuf dFilterVar;
   // The frames a job renders into (float RGB and RGB8 rows, frame-major). On the primary
   // device a job's framebuffers keep a reference to their block until rtMapFrameBuffer reads
   // them back, so the next job renders into the spare (or a fresh) block meanwhile.
@@ -417,6 +419,18 @@ class Device {
     bool inBlock;
   };
   FilterFrame filter_frame(FrameBufferObj& F, int id);
+  // what k_frame_variance reads of F on ctx[0]: the sums and half sums of its last adaptive render
+  // and that render's display mapping; throws (naming `what`) unless F's last frame is an adaptive
+  // render on ctx[0] whose tiles all ran two iterations or more
+  struct VarianceSource {
+    const float4* accu = nullptr;
+    const float4* half = nullptr;
+    float gamma = 1.f, rcpGamma = 1.f;
+    int vignetting = 0;
+  };
+  VarianceSource variance_source(FrameBufferObj& F, const char* what);
+  // yrtFrameVariance: var4 ([H][W][4] floats) of F's last adaptive render to the host
+  void frame_variance(FrameBufferObj& F, float* var4Host);
 };
 
 // yrtDenoiseCube's host check: empty when the six faces of a committed stereo camera are the ideal

@@ -249,6 +249,10 @@ struct FrameBufferObj : Object {
   struct Adaptive {
     uint64_t ctxSerial = 0;
     DevBuf half;  // float4 [height][width]
+    // the tone mapper of the last adaptive render, as its resolve saw it: what the variance of the
+    // displayed frame (yrtFrameVariance, the variance-guided denoiser) maps the halves through
+    float gamma = 1.f, rcpGamma = 1.f;
+    bool vignetting = false;
   };
   std::vector<std::unique_ptr<Adaptive>> adaptive;
   // the last adaptive render's tiles in image tile order (yrtGetAdaptiveTiles): iterations run and

@@ -327,6 +327,10 @@ void RtState::parseCommandLine(const std::vector<std::string>& tokens, const std
       const int v = cin.getInt();
       if (v != 0 && v != 1) throw std::runtime_error("-denoise-cube: 0 or 1 expected");
       denoiseCube = v == 1;
+    } else if (tag == "-denoise-variance") {
+      const int v = cin.getInt();
+      if (v != 0 && v != 1) throw std::runtime_error("-denoise-variance: 0 or 1 expected");
+      denoiseVariance = v == 1;
     } else if (tag == "-depth") {
       depth = cin.getInt();
       check(dev, yrtSetInt1(dev, renderer, "maxDepth", depth), "rtSetInt1");
@@ -622,13 +626,16 @@ void RtState::renderFrame(YRTHandle cam, YRTHandle sc) {
 YRTDenoiseParams RtState::denoiseParams() const {
   YRTDenoiseParams p;
   p.size = (uint32_t)(offsetof(YRTDenoiseParams, iterations) + sizeof(p.iterations));  // the weights: defaults
-  if (denoiseAlbedo) {
-    // the frame is tone mapped: (a L)^(1/gamma) = a^(1/gamma) L^(1/gamma)
+  if (denoiseAlbedo || denoiseVariance) {
     p.size = (uint32_t)sizeof(p);
     if (yrtDenoiseDefaults(&p) != 0) throw std::runtime_error("yrtDenoiseDefaults failed");
+  }
+  if (denoiseAlbedo) {
+    // the frame is tone mapped: (a L)^(1/gamma) = a^(1/gamma) L^(1/gamma)
     p.demodulate = 1;
     p.albedoPower = (float)rcpGamma;
   }
+  if (denoiseVariance) p.varianceGuided = 1;  // sigmaVariance, varianceFloor: the library's defaults
   p.iterations = denoise;
   return p;
 }

@@ -107,6 +107,8 @@ struct RtState {
   int denoise = 0;  // -denoise <iterations>: a-trous passes over every rendered frame (0: off)
   bool denoiseAlbedo = false;  // -denoise-albedo <0|1>: demodulate by the first-hit albedo (with -denoise)
   bool denoiseCube = false;  // -denoise-cube <0|1>: renderCube filters its faces as one surface (with -denoise)
+  // -denoise-variance <0|1>: the variance-guided filter (with -denoise; an error without -adaptive)
+  bool denoiseVariance = false;
   // -adaptive <threshold> <maxIterations>: every frame rendered into frameBuffer is an adaptive
   // render (yrtRenderAdaptive) of -spp samples per iteration; the stereo branch then renders face by face
   bool adaptive = false;
@@ -140,7 +142,7 @@ struct RtState {
   // library's default weights; -denoise-albedo 1: demodulated, albedoPower = 1 / gamma), before it
   // is read, watermarked or assembled into a strip
   void denoiseFrame(YRTHandle cam, YRTHandle sc, YRTHandle fb);
-  YRTDenoiseParams denoiseParams() const;  // what -denoise / -denoise-albedo ask for
+  YRTDenoiseParams denoiseParams() const;  // what -denoise / -denoise-albedo / -denoise-variance ask for
   void outputMode(const std::string& file, std::vector<uint8_t>* outImage = nullptr);
   // FPR branch of outputMode (renderer.cpp:519-737): per camera view, update faceCamera
   // primitives, render the 12 faces, store <dir>/<name>_<camera>.jpg

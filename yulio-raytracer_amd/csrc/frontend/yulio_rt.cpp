@@ -50,6 +50,10 @@ static YRTSession session_new(YRTDevice dev, const std::vector<std::string>& arg
     st.loader.reset(new Loader(st.dev));
     st.createGlobalObjects();
     st.parseCommandLine(args, cwd);
+    // judged once every tag is read, so the tags' order does not matter
+    if (st.denoiseVariance && !st.adaptive)
+      throw std::runtime_error("-denoise-variance 1 needs -adaptive: the variance is estimated from an adaptive "
+                               "render's half buffer");
     return s;
   } catch (const std::exception& e) {
     g_feError = e.what();
@@ -67,6 +71,20 @@ void yrtSessionDestroy(YRTSession s) {
   if (!s) return;
   if (s->st.ownsDevice && s->st.dev) yrtDeleteDevice(s->st.dev);
   delete s;
+}
+
+int yrtSessionDenoiseParams(YRTSession s, YRTDenoiseParams* out) {
+  try {
+    if (!s || !out || out->size < sizeof(uint32_t)) throw std::runtime_error("yrtSessionDenoiseParams: null or unsized struct");
+    const YRTDenoiseParams p = s->st.denoiseParams();
+    const uint32_t n = std::min(out->size, p.size);  // never past either struct
+    memcpy(out, &p, n);
+    out->size = n;
+    return 0;
+  } catch (const std::exception& e) {
+    g_feError = e.what();
+    return -1;
+  }
 }
 
 int yrtSessionInfo(YRTSession s, YRTSessionInfo* out) {

@@ -423,6 +423,35 @@ void launch_atrous(const AtrousParams& ap, int faces, bool wrap, const float4* p
   hipLaunchKernelGGL(kernel, grid, dim3(YRT_BLOCK), 0, s, ap, pos4, nrm4, src, dst, mod4, faceOut);
 }
 
+void launch_frame_variance(const float4* accu, const float4* half, int width, int height, float gamma, float rcpGamma,
+                           int vignetting, float4* var4, hipStream_t s) {
+  const long long n = (long long)width * height;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_frame_variance, dim3((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK)), dim3(YRT_BLOCK), 0, s, accu,
+                     half, width, height, gamma, rcpGamma, vignetting, var4);
+}
+
+void launch_atrous_load_var(const FrameIO* faceIo, int faces, int width, int height, float4* dst,
+                            const Demodulation& dm, const float4* var4, const float4* pos4, hipStream_t s) {
+  const long long n = (long long)width * height;
+  if (n <= 0 || faces <= 0) return;
+  const dim3 grid((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK), (unsigned)faces);
+  hipLaunchKernelGGL(dm.mod4 ? k_atrous_load_var<true> : k_atrous_load_var<false>, grid, dim3(YRT_BLOCK), 0, s, faceIo,
+                     width, height, dst, dm.albedo4, dm.albedoFloor, dm.albedoPower, dm.mod4, var4, pos4);
+}
+
+void launch_atrous_var(const AtrousParams& ap, int faces, bool wrap, const float4* pos4, const float4* nrm4,
+                       const float4* src, float4* dst, const FrameIO* faceOut, const float4* mod4, float sigmaVariance2,
+                       float varianceFloor, hipStream_t s) {
+  const long long n = (long long)ap.width * ap.height;
+  if (n <= 0 || faces <= 0) return;
+  const dim3 grid((unsigned)((n + YRT_BLOCK - 1) / YRT_BLOCK), (unsigned)faces);
+  const auto kernel = mod4 ? (wrap ? k_atrous_var<true, true> : k_atrous_var<true, false>)
+                           : (wrap ? k_atrous_var<false, true> : k_atrous_var<false, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(YRT_BLOCK), 0, s, ap, pos4, nrm4, src, dst, mod4, faceOut, sigmaVariance2,
+                     varianceFloor);
+}
+
 void launch_debug_render(const SceneView& sv, const FrameView& fv, int maxDepth, int spp, int numTiles, float* fbFloat,
                          uint8_t* fbRGB8, int rgb8Stride, hipStream_t s) {
   hipLaunchKernelGGL(k_debug, dim3((numTiles + 63) / 64), dim3(64), 0, s, sv, fv, maxDepth, spp, fbFloat, fbRGB8,

@@ -277,6 +277,19 @@ void launch_atrous_load(const FrameIO* faceIo, int faces, int width, int height,
 // framebuffers (the last one, times the modulation mod4 when that is not null); wrap: the cube's taps
 void launch_atrous(const AtrousParams& ap, int faces, bool wrap, const float4* pos4, const float4* nrm4,
                    const float4* src, float4* dst, const FrameIO* faceOut, const float4* mod4, hipStream_t s);
+// The variance-guided filter (YRTDenoiseParams::varianceGuided, k_frame_variance / k_atrous_load_var /
+// k_atrous_var). launch_frame_variance: var4 = (v_r, v_g, v_b, 1) of one width x height frame as
+// displayed through (gamma, rcpGamma, vignetting), from its sums accu and half sums `half`
+// (common/yrt_pixel_variance.h). The load also stores the scalar variance of the filter's input in
+// dst.w (var4 and pos4 are [face][height][width] arrays), the iterations read and filter it and
+// weigh colours by exp(-|dc|^2 / (sigmaVariance2 vbar + varianceFloor)); rcpSigmaColor2 is not read.
+void launch_frame_variance(const float4* accu, const float4* half, int width, int height, float gamma, float rcpGamma,
+                           int vignetting, float4* var4, hipStream_t s);
+void launch_atrous_load_var(const FrameIO* faceIo, int faces, int width, int height, float4* dst,
+                            const Demodulation& dm, const float4* var4, const float4* pos4, hipStream_t s);
+void launch_atrous_var(const AtrousParams& ap, int faces, bool wrap, const float4* pos4, const float4* nrm4,
+                       const float4* src, float4* dst, const FrameIO* faceOut, const float4* mod4, float sigmaVariance2,
+                       float varianceFloor, hipStream_t s);
 // BVH refit after faceCamera updates: rewrite triangles [firstTri, firstTri+numTris) (global
 // ids) from the vertex buffer in every leaf slot that references them (leafSlots[leafStart[g]
 // .. leafStart[g+1])), then refit one tree level of nodes (call deepest level first)

@@ -413,24 +413,39 @@ class Device:
         return alb
 
     @staticmethod
-    def denoise_defaults(extended=False) -> dict:
-        """The library's default YRTDenoiseParams; extended: with the demodulation fields."""
-        p = N.DenoiseParams(size=C.sizeof(N.DenoiseParams))
-        if N.dev.yrtDenoiseDefaults(C.byref(p)) != 0:
+    def denoise_defaults(extended=False, variance=False) -> dict:
+        """The library's default YRTDenoiseParams; extended: with the demodulation fields;
+        variance: with the variance-guided filter's."""
+        p = N.DenoiseVarianceParams(size=C.sizeof(N.DenoiseVarianceParams))
+        if N.dev.yrtDenoiseDefaults(C.cast(C.pointer(p), C.POINTER(N.DenoiseParams))) != 0:
             raise RuntimeError("yrtDenoiseDefaults failed")
         d = {"iterations": p.iterations, "sigma_color": p.sigmaColor, "sigma_normal": p.sigmaNormal,
              "sigma_position": p.sigmaPosition}
         if extended:
             d.update(demodulate=p.demodulate, albedo_power=p.albedoPower, albedo_floor=p.albedoFloor)
+        if variance:
+            d.update(variance_guided=p.varianceGuided, sigma_variance=p.sigmaVariance, variance_floor=p.varianceFloor)
         return d
 
     @staticmethod
     def _denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_position=None, demodulate=None,
-                        albedo_power=None, albedo_floor=None):
-        """The library's defaults overlaid by the keywords that are not None."""
-        p = N.DenoiseParams(size=C.sizeof(N.DenoiseParams))
-        if N.dev.yrtDenoiseDefaults(C.byref(p)) != 0:
+                        albedo_power=None, albedo_floor=None, variance_guided=None, sigma_variance=None,
+                        variance_floor=None):
+        """A pointer to the library's defaults overlaid by the keywords that are not None: the
+        struct with the variance-guided fields when one of them is given, else the one before them."""
+        long = not (variance_guided is None and sigma_variance is None and variance_floor is None)
+        T = N.DenoiseVarianceParams if long else N.DenoiseParams
+        p = T(size=C.sizeof(T))
+        ptr = C.cast(C.pointer(p), C.POINTER(N.DenoiseParams))
+        ptr._keep = p
+        if N.dev.yrtDenoiseDefaults(ptr) != 0:
             raise RuntimeError("yrtDenoiseDefaults failed")
+        if variance_guided is not None:
+            p.varianceGuided = int(variance_guided)
+        if sigma_variance is not None:
+            p.sigmaVariance = float(sigma_variance)
+        if variance_floor is not None:
+            p.varianceFloor = float(variance_floor)
         if iterations is not None:
             p.iterations = int(iterations)
         if sigma_color is not None:
@@ -445,18 +460,31 @@ class Device:
             p.albedoPower = float(albedo_power)
         if albedo_floor is not None:
             p.albedoFloor = float(albedo_floor)
-        return p
+        return ptr
 
     def denoise(self, camera, scene, frameBuffer, iterations=None, sigma_color=None, sigma_normal=None,
-                sigma_position=None, demodulate=None, albedo_power=None, albedo_floor=None):
+                sigma_position=None, demodulate=None, albedo_power=None, albedo_floor=None, variance_guided=None,
+                sigma_variance=None, variance_floor=None):
         """Filters frameBuffer's current frame in place, guided by the first hits seen through
         `camera` (yrtDenoiseFrameBuffer). None: the library's default (5 iterations, sigma_color 1,
         sigma_normal 64, sigma_position 0.02); sigma_color <= 0 turns the colour weight off.
         demodulate: filter frame / m and store the result x m, m = max(albedo, albedo_floor) ^
-        albedo_power; albedo_power is 1 / gamma of the frame's tone mapper (defaults 0, 1, 1/255)."""
+        albedo_power; albedo_power is 1 / gamma of the frame's tone mapper (defaults 0, 1, 1/255).
+        variance_guided: the colour weight's width is sigma_variance local standard deviations
+        (frame_variance, filtered along with the colour) plus variance_floor instead of
+        sigma_color; frameBuffer must hold an adaptive render (defaults 0, 3, (1/255)^2)."""
         p = self._denoise_params(iterations, sigma_color, sigma_normal, sigma_position, demodulate, albedo_power,
-                                 albedo_floor)
-        self._rc(N.dev.yrtDenoiseFrameBuffer(self.h, camera, scene, frameBuffer, C.byref(p)), "denoise")
+                                 albedo_floor, variance_guided, sigma_variance, variance_floor)
+        self._rc(N.dev.yrtDenoiseFrameBuffer(self.h, camera, scene, frameBuffer, p), "denoise")
+
+    def frame_variance(self, frameBuffer):
+        """var4, float32 (height, width, 4): (v_r, v_g, v_b, 1), the per-pixel variance of the
+        displayed frame of frameBuffer's last adaptive render (yrtFrameVariance)."""
+        w, h = C.c_int32(), C.c_int32()
+        self._rc(N.dev.yrtGetFrameBufferSize(self.h, frameBuffer, C.byref(w), C.byref(h)), "frame_variance")
+        var = np.zeros((h.value, w.value, 4), np.float32)
+        self._rc(N.dev.yrtFrameVariance(self.h, frameBuffer, var.ctypes.data_as(N.PF)), "frame_variance")
+        return var
 
     def denoise_cube(self, cameras, scene, frameBuffers, **kw):
         """The same filter over the 6 (one eye) or 12 faces of a stereo cube as one surface: taps
@@ -469,7 +497,7 @@ class Device:
         p = self._denoise_params(**kw)
         cams = (C.c_void_p * n)(*cameras)
         fbs = (C.c_void_p * n)(*frameBuffers)
-        self._rc(N.dev.yrtDenoiseCube(self.h, cams, n, scene, fbs, C.byref(p)), "denoise_cube")
+        self._rc(N.dev.yrtDenoiseCube(self.h, cams, n, scene, fbs, p), "denoise_cube")
 
     def denoise_times(self):
         """(ms of the last guide pass, ms of the last filter) by HIP events; set_kernel_timing first."""
@@ -717,6 +745,22 @@ def tile_error(accu, half):
     return out
 
 
+def frame_variance(accu, half, gamma=1.0, vignetting=False):
+    """var4 of a frame from its sums `accu` and half sums `half`, float32 (height, width, 4) arrays of
+    (r, g, b, weight), displayed through `gamma` and the vignette: (v_r, v_g, v_b, 1) per pixel, the
+    estimate the variance-guided denoiser filters by (csrc/common/yrt_pixel_variance.h, on the host)."""
+    accu = np.ascontiguousarray(accu, np.float32)
+    half = np.ascontiguousarray(half, np.float32)
+    if accu.ndim != 3 or accu.shape[2] != 4 or half.shape != accu.shape:
+        raise ValueError("accu and half: float32 arrays of one shape (height, width, 4)")
+    h, w = accu.shape[:2]
+    out = np.zeros((h, w, 4), np.float32)
+    if N.dev.yrtDebugFrameVariance(accu.ctypes.data_as(N.PF), half.ctypes.data_as(N.PF), w, h, float(gamma),
+                                   int(bool(vignetting)), out.ctypes.data_as(N.PF)) != 0:
+        raise ValueError("frame_variance: empty frame")
+    return out
+
+
 def cube_tap(W, face, qx, qy):
     """Where the filter tap (qx, qy) of cube face `face` (0..5 within its eye, W x W pixels) lands:
     (g, x, y), the face and pixel, or None for a corner tap, which the cube denoise skips
@@ -786,6 +830,14 @@ class Session:
         if N.fe.yrtSessionInfo(self.h, C.byref(s)) != 0:
             raise RuntimeError(N.fe.yrtFrontendLastError().decode())
         return {n: getattr(s, n) for n, _ in s._fields_}
+
+    def denoise_params(self) -> dict:
+        """The YRTDenoiseParams fields the session's -denoise tags set (yrtSessionDenoiseParams);
+        the fields beyond `size` are left to the library's defaults and not listed."""
+        p = N.DenoiseVarianceParams(size=C.sizeof(N.DenoiseVarianceParams))
+        if N.fe.yrtSessionDenoiseParams(self.h, C.cast(C.pointer(p), C.POINTER(N.DenoiseParams))) != 0:
+            raise RuntimeError(N.fe.yrtFrontendLastError().decode())
+        return {n: getattr(p, n) for n, t in p._fields_ if getattr(N.DenoiseVarianceParams, n).offset < p.size}
 
     def camera(self, face=-1):
         h = N.fe.yrtSessionCamera(self.h, face)

@@ -87,6 +87,12 @@ class DenoiseParams(C.Structure):
                 ("sigmaPosition", f32), ("demodulate", i32), ("albedoPower", f32), ("albedoFloor", f32)]
 
 
+class DenoiseVarianceParams(C.Structure):
+    """YRTDenoiseParams as it stands today, with the variance-guided fields at its end;
+    DenoiseParams is the header's struct before them, which the library reads by its size."""
+    _fields_ = DenoiseParams._fields_ + [("varianceGuided", i32), ("sigmaVariance", f32), ("varianceFloor", f32)]
+
+
 class AdaptiveParams(C.Structure):
     """include/yrt_device.h YRTAdaptiveParams; size = the bytes the caller's struct holds."""
     _fields_ = [("size", C.c_uint32), ("threshold", f32), ("minIterations", i32), ("maxIterations", i32)]
@@ -250,6 +256,12 @@ try:  # adaptive sampling; absent from older builds selected with YRT_LIB_DIR
     _sig(dev, "yrtDebugTileError", i32, PF, PF, i32, i32, PF)
 except AttributeError:
     pass
+try:  # the variance-guided denoise; absent from older builds selected with YRT_LIB_DIR
+    _sig(dev, "yrtFrameVariance", i32, vp, vp, PF)
+    _sig(dev, "yrtGetFrameBufferSize", i32, vp, vp, C.POINTER(i32), C.POINTER(i32))
+    _sig(dev, "yrtDebugFrameVariance", i32, PF, PF, i32, i32, f32, i32, PF)
+except AttributeError:
+    pass
 _sig(dev, "yrtDebugDecodeImage", i32, cstr, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, sz)
 _sig(dev, "yrtDebugSampleTable", i32, i32, i32, i32, i32, i32, cstr, PF, sz)
 
@@ -259,6 +271,10 @@ _sig(fe, "yrtSessionDestroy", None, vp)
 _sig(fe, "yrtFrontendLastError", cstr)
 _sig(fe, "yrtSessionInfo", i32, vp, C.POINTER(SessionInfo))
 _sig(fe, "yrtSessionCamera", vp, vp, i32)
+try:  # absent from older builds selected with YRT_LIB_DIR
+    _sig(fe, "yrtSessionDenoiseParams", i32, vp, C.POINTER(DenoiseParams))
+except AttributeError:
+    pass
 _sig(fe, "yrtSessionRender", vp, vp, i32)
 _sig(fe, "yrtSessionRenderCube", i32, vp)
 _sig(fe, "yrtSessionRenderSceneCube", i32, vp, i32)
